@@ -14,7 +14,18 @@ the hot path over one batch of `--rays` rays per GPU, inputs already resident in
 N>1 shards the rays of ONE global batch of `--rays` rays contiguously across the ranks (BASELINE.json configs[2] as SURVEY 8d defines it:
 "scaling": "strong"), point cloud and MLP replicated; `--weak` keeps `--rays` rays PER GPU instead (the optional weak-scaling variant);
 the only collectives are the gradient all-reduce and a 2-float loss normaliser.
-Rank 0 prints ONE JSON line; `value` is whole-job rays/sec.  `roofline` (dominant kernel): `frac` = SURVEY 8d algorithmic work / nominal peak,
+Rank 0 prints ONE JSON line; `value` is whole-job rays/sec.  A plain run sets up, warms up, times `--steps` steps and prints that line
+(`ms_per_step` = wall milliseconds of one timed step); everything else it can measure runs only with `--full`: per-kernel HIP events in the
+timed steps and the roofline, the cold-grid and no-optimizer steps, the supplementary variants and the CPU baseline.
+With `--dump-outputs DIR` the last timed step starts from the seeded initial parameters and fresh Adam moments, restored in place
+(~1 GB of device copies once per run; their device time, timed with events, is not counted in the steps' wall time).  The backward sums
+gradients with float atomics, and Adam amplifies their rounding over chained steps: without the restore, what the last step computes
+would differ from run to run.  With it, that step's inputs (batch, parameters, optimizer state, jitter seed) are the same for the same
+arguments, its forward is bit-reproducible, and its gradients and update differ only by the order of the atomic additions.  It writes
+what that step computed (loss, ray colours and mask, parameters after the update and their gradients, point tensors as a fixed seeded
+sample of rows) as DIR/<name>.npy in float32 (gradient sums in float64); `config.final_loss` stays the loss of the step before it, the
+last of the training trajectory, and `config.dump` holds the dumped step's loss.  Without `--dump-outputs` nothing is restored.
+`roofline` (`--full`, dominant kernel): `frac` = SURVEY 8d algorithmic work / nominal peak,
 `frac_executed` = executed f16 products / nominal peak, `peak_measured` = the ceiling timed in this run (f16 MFMA with toggling operands:
 pnerf_debug_mfma_rate; HBM entries: a 1 GiB device copy), `traffic` = PMC bytes of the committed profile pass (stamped with its commit).
 `cpu_baseline`: kind "port" (oracle) on the GPU box, "reference" where /root/reference imports (`--cpu-baseline-only`).
@@ -96,6 +107,68 @@ def _cfg():
 
 
 CONFIGS = ("barn", "chair", "lego", "scannet")
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_POINT_ROWS = 65536          # rows of each per-point tensor written by --dump-outputs (a fixed seeded sample; all rows below that count)
+DUMP_ROW_SEED = 0
+
+
+def reset_training_state(params, init, optimizers):
+    """the seeded initial parameters and fresh optimizer state (step 0, zero moments), in place: no allocation, the addresses (gradient
+    bucket views, ShardedAdam's flat buffer) are unchanged"""
+    from pointnerf_amd.optim import ShardedAdam
+    with torch.no_grad():
+        torch._foreach_copy_([p.data for p in params], list(init))
+        moments = []
+        for o in optimizers:
+            if isinstance(o, ShardedAdam):
+                o.step_count = 0
+                moments += [o.exp_avg, o.exp_avg_sq]
+            else:
+                for st in o.state.values():
+                    st["step"].zero_()
+                    moments += [st["exp_avg"], st["exp_avg_sq"]]
+        torch._foreach_zero_(moments)
+
+
+def dump_outputs(path, out, loss, mlp_named, pt_named):
+    """--dump-outputs: what the caller of the timed step receives from its last step, as float32 .npy files under `path`.
+    `out`: the model's output dict; `mlp_named` / `pt_named`: (name, parameter) pairs, read after the optimizer step (their .grad are
+    the step's gradients).  Per-point tensors are sampled at DUMP_POINT_ROWS rows drawn with DUMP_ROW_SEED (sorted), the same rows for
+    the same point count, plus the float64 sum of |gradient| over all rows."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": np.array([float(loss.detach().float().item())], dtype=np.float32)}
+    if "_dense_color" in out:                     # fused colour loss: dense ray colours + hit flags; hit rays in ascending ray order
+        color, hit = out["_dense_color"][0], out["_dense_color"][1] > 0
+        arrays["coarse_raycolor"] = color.detach()[hit]
+    else:                                         # compacted [1, hit rays, 3], ascending ray order
+        arrays["coarse_raycolor"] = out["coarse_raycolor"].detach()[0]
+    arrays["ray_mask"] = out["ray_mask"].detach()[0]
+    for name, p in mlp_named:
+        arrays["mlp." + name] = p.detach()
+        if p.grad is not None:
+            arrays["mlp_grad." + name] = p.grad.detach()
+    if pt_named:
+        n = pt_named[0][1].shape[-2]                  # [1, points, channels]
+        rows = np.arange(n) if n <= DUMP_POINT_ROWS else np.sort(np.random.default_rng(DUMP_ROW_SEED).choice(n, DUMP_POINT_ROWS, replace=False))
+        rows_d = torch.from_numpy(rows).to(pt_named[0][1].device)
+        grad_abs = []
+        for name, p in pt_named:
+            arrays[name] = p.detach().reshape(n, -1).index_select(0, rows_d)
+            if p.grad is not None:
+                arrays[name + "_grad"] = p.grad.detach().reshape(n, -1).index_select(0, rows_d)
+                grad_abs.append(float(p.grad.detach().double().abs().sum()))
+        if grad_abs:
+            arrays["points_grad_abs_sum"] = np.array(grad_abs, dtype=np.float64)
+    total = 0
+    for name, a in arrays.items():
+        a = a.float().cpu().numpy() if isinstance(a, torch.Tensor) else a
+        arrays[name] = a
+        total += a.nbytes
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def parse():
@@ -128,6 +201,13 @@ def parse():
                     help="bring-up on a 1-GPU box: --gpus 1 with a one-rank RCCL group and EVERY collective of the step executed (as identities): the "
                          "calls, streams and in-place forms the 8-GPU run will make, on the real backend")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="no GPU: time only the cpu_baseline leg (kind reference where /root/reference imports, else port) and print it")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: per-kernel HIP events in the timed steps + roofline (with a device copy and a "
+                         "matrix-pipe run of their own), the cold-grid and no-optimizer steps, the supplementary variants (--no-variants, "
+                         "--no-fp32-class-variant) and the CPU baseline (--cpu-rays); without it a run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; float64 for the gradient sums; "
+                         "%d MB at most)" % (DUMP_LIMIT_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -332,6 +412,11 @@ def rccl_selftest(dev, rank, world):
     return "ok backend=%s world=%d" % (backend, world)
 
 
+def cpu_threads():
+    """host threads of the CPU baseline: OMP_NUM_THREADS where the launcher sets it (the cores this process may use), else every core; 32 at most"""
+    return min(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1, 32)
+
+
 def best_cpu_baseline(opt, n_points, rays, threads, points_fn=None, rays_fn=None):
     """`reference` when the reference's modules import (only where /root/reference exists), the port otherwise (the GPU box)"""
     if os.path.isdir("/root/reference/models/aggregators"):
@@ -348,7 +433,7 @@ def main():
     args = parse()
     if args.cpu_baseline_only:
         cfg_name, opt_fn, points_fn, n_default, rays_fn = _cfg()[args.config]
-        print(json.dumps(best_cpu_baseline(opt_fn(is_train=1), args.points or n_default, args.cpu_rays, min(os.cpu_count() or 1, 32), points_fn, rays_fn)))
+        print(json.dumps(best_cpu_baseline(opt_fn(is_train=1), args.points or n_default, args.cpu_rays, cpu_threads(), points_fn, rays_fn)))
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -438,19 +523,25 @@ def _run(args, world, rank, dev, dist_on, selftest, rearm):
     sparse = dist_on and not zero1 and (args.point_grads == "sparse" or (args.point_grads == "auto" and n_points >= 6_000_000))
     opt_mlp = FusedAdam(mlp_params, lr=opt.lr, betas=(0.9, 0.999))
     opt_pts = ShardedAdam(pt_params, lr=opt.plr, betas=(0.9, 0.999)) if zero1 else FusedAdam(pt_params, lr=opt.plr, betas=(0.9, 0.999))
+    # the seeded initial state (after ShardedAdam re-homed the point parameters): the last timed step starts from it (reset_training_state)
+    init_state = [p.detach().clone() for p in mlp_params + pt_params] if (args.dump_outputs and not args.render_only) else None
 
     comm_marks = None                         # (event pairs around the gradient exchange on the main stream; filled in the timed region)
     total = args.warmup + args.steps
     inputs = [step_inputs(i, rank, world, rays_rank, dev, rays_fn) for i in range(total)]   # resident in HBM before timing
 
-    def one_step(inp):
+    def one_step(inp, keep=None):
         nonlocal comm_marks
         if args.render_only:
             with torch.no_grad():
                 out = model(**inp)
+            if keep is not None:
+                keep["out"] = out
             return out["coarse_raycolor"].sum(), model.last_stats
         opt_mlp.zero_grad(set_to_none=True); opt_pts.zero_grad(set_to_none=True)
         out = model(**inp)
+        if keep is not None:
+            keep["out"] = out
         loss = loss_fn(opt, out, inp, world)
         loss.backward()
         if dist_on and comm_marks is not None:
@@ -496,12 +587,15 @@ def _run(args, world, rank, dev, dist_on, selftest, rearm):
     # set-up, not warm-up: two untimed steps on the first batch size the activation arena (one ~80 GB hipMalloc) and let the caching
     # allocator settle, so that the measurement does not depend on how many warm-up steps the caller asks for
     for _ in range(2):
-        one_step(inputs[0])
+        loss, _ = one_step(inputs[0])
     for i in range(args.warmup):
-        one_step(inputs[i])
+        loss, _ = one_step(inputs[i])
+    if init_state is not None:                         # the reset's kernels loaded before the timed region (their first launch loads code)
+        torch._foreach_zero_([torch.empty(1, device=dev)]); torch._foreach_copy_([torch.empty(1, device=dev)], [torch.zeros(1, device=dev)])
     torch.cuda.synchronize()
     rearm("the timed steps")
-    if not args.no_prof:
+    prof_on = args.full and not args.no_prof          # per-kernel HIP events around every library launch of the timed steps
+    if prof_on:
         ops.prof_enable(True)
         ops.prof_collect()
     if dist_on:
@@ -510,34 +604,61 @@ def _run(args, world, rank, dev, dist_on, selftest, rearm):
     allocs0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]      # step boundaries on the stream the kernels run on
     comm_marks = [] if dist_on else None
+    last = {}                                          # the output dict of the last timed step (--dump-outputs)
+    reset_marks = pre_reset_finite = None
+    timed_losses = []                                  # every timed step's loss (device scalars: read once, after the timing)
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.warmup, total):
-        loss, st = one_step(inputs[i])
+        if i == total - 1 and init_state is not None:      # --dump-outputs: same inputs every run (module docstring); not part of a step
+            chained_loss = loss                            # the loss of the last step of the trajectory (config.final_loss)
+            reset_marks = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            reset_marks[0].record()
+            pre_reset_finite = torch.stack([torch.isfinite(p).all() for p in mlp_params + pt_params]).all()     # (no host read here)
+            reset_training_state(mlp_params + pt_params, init_state, [opt_mlp, opt_pts])
+            reset_marks[1].record()
+        loss, st = one_step(inputs[i], keep=last if i == total - 1 else None)
+        timed_losses.append(loss.detach())
         marks[i - args.warmup + 1].record()
         stats.append(st)
+    if reset_marks is None:
+        chained_loss = loss
     torch.cuda.synchronize()
     if dist_on:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    reset_ms = reset_marks[0].elapsed_time(reset_marks[1]) if reset_marks is not None else 0.0
+    dt = time.perf_counter() - t0 - reset_ms * 1e-3
     extra_allocs = torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0      # hipMalloc calls inside the timed region
     prof = None
-    if not args.no_prof:
+    if prof_on:
         prof = ops.prof_collect()
         ops.prof_enable(False)
-    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) - (reset_ms if i == args.steps - 1 else 0.0) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
     dt_local = dt
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if dist_on:
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
+    # a NaN / Inf anywhere in the timed steps (any step's loss, the parameters before the --dump-outputs reset and after the last update)
+    # makes the number meaningless
+    finite = bool(torch.isfinite(torch.stack(timed_losses)).all()) and (pre_reset_finite is None or bool(pre_reset_finite)) \
+        and all(bool(torch.isfinite(p).all()) for p in mlp_params + pt_params)
+    if not finite and not os.environ.get("PNERF_BENCH_ALLOW_NAN"):      # (the env switch exists for dev variants that drop work on purpose)
+        raise SystemExit("bench.py: non-finite loss or parameters in the timed steps -- the timed path produced NaN/Inf, the number would be meaningless")
+    if args.dump_outputs and rank == 0:                # before anything else runs a step: the parameters are those the last timed step left
+        mlp_named = [(n, p) for n, p in agg.named_parameters() if p.requires_grad] if not args.render_only else []
+        pt_named = [(n, getattr(npnt, n)) for n in ("points_embeding", "points_conf", "points_dir", "points_color")
+                    if getattr(npnt, n).requires_grad] if not args.render_only else []
+        dump_outputs(args.dump_outputs, last["out"], loss, mlp_named, pt_named)
+    dumped_loss = float(loss.item())
+    del last, init_state, timed_losses
 
-    # supplementary, outside the timed region: one step with the voxel grid rebuilt (what the reference pays every
+    # supplementary (--full), outside the timed region: one step with the voxel grid rebuilt (what the reference pays every
     # step: query_worldcoords.cu:308-365), and one step without the optimizer
     extra = {}
-    if not args.render_only:
+    if args.full and not args.render_only:
         from pointnerf_amd import point_query
         def timed(fn):
             torch.cuda.synchronize(); t = time.perf_counter(); fn(); torch.cuda.synchronize()
@@ -625,7 +746,7 @@ def _run(args, world, rank, dev, dist_on, selftest, rearm):
                                                        "tests/test_gpu_zz_convergence.py, tests/test_gpu_bench_config.py compare the two"}
             finally:
                 ops.set_wgrad_planes(1)
-    if not np.isfinite(float(loss.item())) and not os.environ.get("PNERF_BENCH_ALLOW_NAN"):      # (the env switch exists for dev variants that drop work on purpose)
+    if not np.isfinite(float(chained_loss.item())) and not os.environ.get("PNERF_BENCH_ALLOW_NAN"):      # (the env switch exists for dev variants that drop work on purpose)
         raise SystemExit("bench.py: non-finite loss after %d steps -- the timed path produced NaN/Inf, the number would be meaningless" % total)
     per_rank_ms = [dt / args.steps * 1e3]
     exposed_ms = replica_spread = None
@@ -668,8 +789,9 @@ def _run(args, world, rank, dev, dist_on, selftest, rearm):
                                           "configuration is HIP-vs-oracle truncation only (pointnerf_amd/config.py barn_opt)") if args.config == "barn" else None,
                           "parallelism": "ray-shard dp%d, point cloud + MLP replicated" % world, "point_grad_exchange": ("none" if not dist_on else ("zero1 reduce-scatter" if zero1 else ("sparse touched rows" if sparse else "dense all-reduce, one bucket, overlapped"))), "world_size": world, "ms_per_step_by_rank": per_rank_ms, "ms_allreduce_exposed_by_rank": exposed_ms, "replica_param_checksum_spread": replica_spread,
                           "valid_samples_per_step": smp, "neighbor_rows_per_step": rows,
-                          "rays_hit_per_step": float(np.mean([s["rays_hit"] for s in stats])), "final_loss": float(loss.item()),
+                          "rays_hit_per_step": float(np.mean([s["rays_hit"] for s in stats])), "final_loss": float(chained_loss.item()),
                           "device_allocs_in_timed_region": int(extra_allocs), "setup_steps": 2,
+                          "dump": None if reset_marks is None else {"loss_of_dumped_step": dumped_loss, "ms_state_reset_before_last_step": reset_ms},
                           "saved_activation_bytes_per_step": int(ops.L.lib().pnerf_agg_saved_bytes(int(smp), int(opt.K))),
                           "arena_budget_bytes": ops.arena_budget_bytes(),
                           "backward_ray_chunks": None if getattr(FusedRender, "last_chunks", None) is None else
@@ -759,9 +881,9 @@ def _run(args, world, rank, dev, dist_on, selftest, rearm):
             for k in alg_flop:
                 if k in per:
                     out["kernels"][k]["tflops"] = alg_flop[k] / (per[k]["ms_per_step"] * 1e-3) / 1e12
-        if not dist_on and args.cpu_rays > 0 and not args.render_only and args.config in ("lego", "chair"):
+        if args.full and not dist_on and args.cpu_rays > 0 and not args.render_only and args.config in ("lego", "chair"):
             try:
-                out["cpu_baseline"] = best_cpu_baseline(opt, n_points, args.cpu_rays, min(os.cpu_count() or 1, 32), points_fn, rays_fn)
+                out["cpu_baseline"] = best_cpu_baseline(opt, n_points, args.cpu_rays, cpu_threads(), points_fn, rays_fn)
                 if out["cpu_baseline"].get("kind") == "port":
                     out["cpu_baseline"]["note"] = ("kind 'port': /root/reference does not exist on a GPU box (the checkout cannot travel), so the oracle's restatement is "
                                                    "timed here; the reference's own modules on host cores (kind 'reference': its query kernels compiled for the host + "

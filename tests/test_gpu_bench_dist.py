@@ -20,7 +20,7 @@ def _last_json(out):
 
 def test_bench_json_contract_single_gpu():
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--rays", "8192",
-                                   "--points", "300000", "--cpu-rays", "64"], cwd=ROOT, timeout=900)
+                                   "--points", "300000", "--cpu-rays", "64", "--full"], cwd=ROOT, timeout=900)
     d = _last_json(out)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -45,10 +45,48 @@ def test_bench_json_contract_single_gpu():
     assert hb["survey_algorithmic_bytes_per_step"] > 0 and d["cpu_baseline"].get("note") or d["cpu_baseline"]["kind"] == "reference"
     # and the mode can be timed on its own
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--rays", "8192",
-                                   "--points", "300000", "--cpu-rays", "0", "--wgrad-planes", "2"], cwd=ROOT, timeout=900)
+                                   "--points", "300000", "--cpu-rays", "0", "--wgrad-planes", "2", "--full"], cwd=ROOT, timeout=900)
     d2 = _last_json(out)
     assert d2["config"]["wgrad_planes"] == 2 and "fp32_class_variant" not in d2["config"] and "3 products" in d2["dtype"]
     assert abs(d2["config"]["final_loss"] - d["config"]["final_loss"]) <= 1e-4 * max(1.0, abs(d["config"]["final_loss"]))
+
+
+def test_plain_bench_times_only_the_headline_and_dumps_its_last_step(tmp_path):
+    """without --full the line carries the headline and nothing that needs runs of its own; --dump-outputs writes the last timed step's
+    results (float32 / float64, 64 MB at most), and two runs with the same arguments compute the same from the same inputs"""
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--rays", "8192", "--points", "300000"]
+    runs = []
+    for tag in ("a", "b"):
+        d = _last_json(subprocess.check_output(base + ["--dump-outputs", str(tmp_path / tag)], cwd=ROOT, timeout=900))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "rays/s"
+        for k in ("roofline", "roofline_mfma", "roofline_hbm", "kernels", "ms_outside_library_kernels", "cpu_baseline"):
+            assert k not in d, k
+        for k in ("ms_step_cold_grid", "ms_step_without_optimizer", "f16_cross_terms_variant", "e4m3_forward_variant", "reference_shell_variant",
+                  "fp32_class_variant"):
+            assert k not in d["config"], k
+        files = sorted(os.listdir(str(tmp_path / tag)))
+        arrays = {f[:-4]: np.load(str(tmp_path / tag / f)) for f in files}
+        assert all(f.endswith(".npy") for f in files) and all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(str(tmp_path / tag / f)) for f in files) <= 64 << 20
+        for k in ("loss", "coarse_raycolor", "ray_mask", "points_embeding", "points_embeding_grad", "mlp.block1.0.weight", "mlp_grad.block1.0.weight"):
+            assert k in arrays, k
+        assert all(np.isfinite(a).all() for a in arrays.values())
+        assert float(arrays["loss"][0]) == np.float32(d["config"]["dump"]["loss_of_dumped_step"])
+        assert np.isfinite(d["config"]["final_loss"]) and d["config"]["dump"]["ms_state_reset_before_last_step"] >= 0
+        assert arrays["coarse_raycolor"].shape == (int(arrays["ray_mask"].sum()), 3) and arrays["points_embeding"].shape == (65536, 32)
+        runs.append(arrays)
+    a, b = runs
+    assert sorted(a) == sorted(b) and all(a[k].shape == b[k].shape for k in a)
+    # the last step starts from the seeded initial state: its forward is bit-reproducible, gradients and update differ by the order of
+    # the backward's atomic additions only
+    assert np.array_equal(a["ray_mask"], b["ray_mask"]) and np.array_equal(a["coarse_raycolor"], b["coarse_raycolor"])
+    assert abs(float(a["loss"][0]) - float(b["loss"][0])) <= 1e-6 * abs(float(a["loss"][0]))
+    for k in a:
+        scale = max(float(np.abs(a[k]).max()), 1e-30)
+        assert float(np.abs(a[k].astype(np.float64) - b[k]).max()) <= 1e-4 * scale, (k, float(np.abs(a[k].astype(np.float64) - b[k]).max()), scale)
 
 
 def test_bench_refuses_a_gpu_count_it_was_not_launched_with():

@@ -10,7 +10,7 @@ for rep in 1 2; do
 for V in shipped "$@"; do
   [ $V != shipped ] && cp tools/_build/$V.so pointnerf_amd/libpnerf_hip.so
   [ $V == shipped ] && cp /tmp/shipped.so pointnerf_amd/libpnerf_hip.so
-  timeout 600 python bench.py --config barn --cpu-rays 0 --steps 5 --warmup 2 --no-fp32-class-variant > $O/barn_${V}_$rep.json 2>$O/barn_$V.err
+  timeout 600 python bench.py --full --config barn --cpu-rays 0 --steps 5 --warmup 2 --no-fp32-class-variant > $O/barn_${V}_$rep.json 2>$O/barn_$V.err
   python - <<PY
 import json
 try:

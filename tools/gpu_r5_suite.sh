@@ -10,4 +10,4 @@ timeout 3000 python -m pytest tests -m gpu -x -q --durations=12 -rs "$@" > $O/te
 echo "pytest rc=$? wall=$(( $(date +%s) - S )) s" | tee -a $O/tests.log
 grep -v amdgpu.ids $O/tests.log | tail -45
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.log
-timeout 600 python bench.py > $O/bench_lego.json 2>$O/bench_lego.err; tail -c 600 $O/bench_lego.json
+timeout 600 python bench.py --full > $O/bench_lego.json 2>$O/bench_lego.err; tail -c 600 $O/bench_lego.json

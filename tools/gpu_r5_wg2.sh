@@ -10,7 +10,7 @@ cp pointnerf_amd/libpnerf_hip.so /tmp/shipped.so
 for V in shipped "$@" shipped; do
   [ $V != shipped ] && cp tools/_build/$V.so pointnerf_amd/libpnerf_hip.so
   [ $V == shipped ] && cp /tmp/shipped.so pointnerf_amd/libpnerf_hip.so
-  timeout 300 python bench.py --cpu-rays 0 --steps 10 --wgrad-planes 2 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --cpu-rays 0 --steps 10 --wgrad-planes 2 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']; print('$V', 'planes 2:', round(d['value']), 'rays/s', round(d['ms_per_step'],2), 'ms  fwd', round(k['agg_forward']['ms_per_step'],2), 'bwd', round(k['agg_backward']['ms_per_step'],2), 'wgrad', round(k['wgrad']['ms_per_step'],2), 'reduce', round(k['wgrad_reduce']['ms_per_step'],2), 'loss', d['config']['final_loss'])"
 done
 cp /tmp/shipped.so pointnerf_amd/libpnerf_hip.so

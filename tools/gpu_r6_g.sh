@@ -1,7 +1,7 @@
 #!/bin/bash
 cd $GRAFT_REPO_ROOT
 T=${1:-r6_g}; O=gpurun_out/$T; mkdir -p $O
-python bench.py --steps 12 --warmup 4 --no-variants > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -3 $O/bench.err
+python bench.py --full --steps 12 --warmup 4 --no-variants > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -3 $O/bench.err
 python - <<P
 import json
 d=json.load(open("$O/bench.json"))

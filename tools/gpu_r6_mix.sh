@@ -8,7 +8,7 @@ for M in 5 7; do
   echo "mask $M rc $?"; tail -4 $O/tests_mask$M.log
 done
 for M in 7 5 0; do
-  PNERF_MIX_MASK=$M python bench.py --steps 10 --warmup 4 > $O/bench_mask$M.json 2> $O/bench_mask$M.err
+  PNERF_MIX_MASK=$M python bench.py --full --steps 10 --warmup 4 > $O/bench_mask$M.json 2> $O/bench_mask$M.err
   python - <<P
 import json
 d=json.load(open("$O/bench_mask$M.json"))

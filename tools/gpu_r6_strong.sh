@@ -6,7 +6,7 @@ T=${1:-r6_strong}; O=gpurun_out/$T; mkdir -p $O
 for R in 8192 16384 32768 65536; do
   for X in dense sparse zero1; do
     if [ $X = zero1 ]; then F="--zero1"; else F="--point-grads $X"; fi
-    python bench.py --steps 12 --warmup 4 --rays $R --force-collectives --no-variants --cpu-rays 0 $F > $O/b_${R}_$X.json 2> $O/b_${R}_$X.err || tail -3 $O/b_${R}_$X.err
+    python bench.py --full --steps 12 --warmup 4 --rays $R --force-collectives --no-variants --cpu-rays 0 $F > $O/b_${R}_$X.json 2> $O/b_${R}_$X.err || tail -3 $O/b_${R}_$X.err
   done
 done
 python - <<P

@@ -3,11 +3,11 @@
 # passes), matrix-pipe / wait counters, the micro-benchmarks.  Usage: bash tools/gpu_round_profile.sh <tag>  -> gpurun_out/<tag>/
 cd $GRAFT_REPO_ROOT
 T=$1; O=gpurun_out/$T; mkdir -p $O
-timeout 600 python bench.py --steps 20 --warmup 3 > $O/bench_lego.json 2>$O/bench_lego.err
-timeout 300 python bench.py --steps 10 --warmup 2 --render-only --cpu-rays 0 > $O/bench_render_only.json 2>$O/bench_render_only.err
-timeout 300 python bench.py --steps 10 --warmup 2 --render-only --inference-products 2 --cpu-rays 0 > $O/bench_render_only_2products.json 2>/dev/null
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $O/bench_lego.json 2>$O/bench_lego.err
+timeout 300 python bench.py --full --steps 10 --warmup 2 --render-only --cpu-rays 0 > $O/bench_render_only.json 2>$O/bench_render_only.err
+timeout 300 python bench.py --full --steps 10 --warmup 2 --render-only --inference-products 2 --cpu-rays 0 > $O/bench_render_only_2products.json 2>/dev/null
 for C in chair scannet barn; do
-  timeout 600 python bench.py --config $C --steps 5 --warmup 2 --cpu-rays 0 > $O/bench_$C.json 2>$O/bench_$C.err
+  timeout 600 python bench.py --full --config $C --steps 5 --warmup 2 --cpu-rays 0 > $O/bench_$C.json 2>$O/bench_$C.err
 done
 timeout 900 bash tools/gpu_profile.sh $T > $O/profile.log 2>&1
 timeout 600 bash tools/gpu_pmc_mfma.sh $T > $O/pmc_mfma.log 2>&1
