@@ -181,6 +181,8 @@ typedef struct pnerf_point_grads {   /* gradient accumulators (added to, never z
                                       * ((#rays hit x SR x K - #valid neighbor slots) identical terms): the regulariser's own pass of ~7 M atomics on
                                       * the same addresses is not run */
     float zero_one_eps;              /* its clamp bound (opt.zero_epsilon) */
+    float *xyz;                      /* optional [N,3] (NULL: none; pnerf_render_backward only): d xyz of the point positions (xyz_grad), through
+                                      * the distance encoding and the inverse-distance weights of every neighbor row that names the point */
 } pnerf_point_grads;
 
 /* bytes of saved activations per valid neighbor row / per valid sample (training forward) */

@@ -24,13 +24,13 @@ extern "C" int pnerf_mlp_layout(int feat_dim, int64_t *offsets) {
     for (int i = 0; i <= PNERF_MLP_NTENSORS; ++i) offsets[i] = o[i];
     return 0;
 }
-extern "C" size_t pnerf_mlp_packed_bytes(void) { return (size_t)PKM_END; }
+extern "C" size_t pnerf_mlp_packed_bytes(void) { return (size_t)PKX_END; }
 
 namespace {
 // two-plane f16 images of the aggregator and colour layers (f16x3.h): forward W[m][k] (trans = 0: m = output unit, k = input column)
 // and dgrad W^T[m][k] (trans = 1: m = input column, k = output unit)
 struct PackHDesc { int src, ld, trans, Mreal, Kreal, NCH, MB, dst; };
-struct PackHTable { PackHDesc d[14]; };
+struct PackHTable { PackHDesc d[15]; };
 __global__ __launch_bounds__(256) void k_pack_h(PackHTable t, const float *__restrict__ params, char *__restrict__ packed) {
     const PackHDesc d = t.d[blockIdx.y];
     const int total = d.NCH * d.MB * 64;
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void k_pack_h(PackHTable t, const float *__res
 // mixed-format images of the eight aggregator GEMMs (mixq.h): per (superchunk, feature block, lane) four f16 h fragments, two e4m3 fragments
 // [q8(wm 2^11 / 2^e) x 8 | q8(wh / 2^e) x 8] per 8-column group with the lane's block scale e, then the classic two-plane tail chunks
 struct PackMDesc { int src, ld, trans, Mreal, Kreal, NT, MB, dst; };
-struct PackMTable { PackMDesc d[8]; };
+struct PackMTable { PackMDesc d[9]; };
 __global__ __launch_bounds__(256) void k_pack_mix(PackMTable t, const float *__restrict__ params, char *__restrict__ packed) {
     pn_mode_saturate();
     const PackMDesc d = t.d[blockIdx.y];
@@ -164,9 +164,11 @@ extern "C" int pnerf_mlp_pack(const float *d_params, void *d_packed, void *strea
         {PO_WC3, PN_HC, 1, PN_HC, PN_HC, 8, 4, PKH_DC3},
         {PO_WC2, PN_HC, 1, PN_HC, PN_HC, 8, 4, PKH_DC2},
         {PO_WC1, PN_INC, 1, PN_H, PN_HC, 8, 8, PKH_DC1},
+        // xyz_grad: d X0 columns 224 .. 287 (W1^T rows 224 .. 283, the distance encoding; rows 284 .. 287 zero)
+        {PO_W1 + 32 * PN_MB_D1, PN_IN1, 1, PN_IN1 - 32 * PN_MB_D1, PN_H, 16, 2, PKH_D1T},
     }};
     PnProfScope prof(PNK_PACK, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_pack_h, dim3(40, 14), dim3(256), 0, (hipStream_t)stream, th, d_params, (char *)d_packed);
+    hipLaunchKernelGGL(k_pack_h, dim3(40, 15), dim3(256), 0, (hipStream_t)stream, th, d_params, (char *)d_packed);
     PackMTable tm = {{
         {PO_W1, PN_IN1, 0, PN_H, PN_IN1, 2, 8, PKM_F1},
         {PO_W2, PN_H, 0, PN_H, PN_H, 0, 8, PKM_F2},
@@ -176,8 +178,9 @@ extern "C" int pnerf_mlp_pack(const float *d_params, void *d_packed, void *strea
         {PO_W3, PN_IN3, 1, PN_IN3, PN_H, 0, 9, PKM_D3},
         {PO_W2, PN_H, 1, PN_H, PN_H, 0, 8, PKM_D2},
         {PO_W1, PN_IN1, 1, 32 * PN_MB_D1, PN_H, 0, PN_MB_D1, PKM_D1},
+        {PO_W1 + 32 * PN_MB_D1, PN_IN1, 1, PN_IN1 - 32 * PN_MB_D1, PN_H, 0, 2, PKM_D1T},
     }};
-    hipLaunchKernelGGL(k_pack_mix, dim3(12, 8), dim3(256), 0, (hipStream_t)stream, tm, d_params, (char *)d_packed);
+    hipLaunchKernelGGL(k_pack_mix, dim3(12, 9), dim3(256), 0, (hipStream_t)stream, tm, d_params, (char *)d_packed);
     PN_CHECK_LAUNCH();
     return 0;
 }

@@ -38,6 +38,14 @@ struct BwdArgs {
     const float *conf, *zo_gs;
     float zo_eps;
 };
+// the xyz_grad instances' arguments (pnerf_point_grads.xyz): d xyz, and what its chain recomputes the distances from.  A type of its own, so
+// that the kernel arguments of the other instances -- and with them the offsets of their implicit arguments -- stay as they are
+struct BwdXArgs : BwdArgs {
+    const float *xyz, *sample_loc;
+    float *g_xyz;
+};
+template <bool XYZG> struct BwdArgsOf { using T = BwdArgs; };
+template <> struct BwdArgsOf<true> { using T = BwdXArgs; };
 
 // d/d conf of log(v) + log(1 - v), v = clamp(clamp(conf, 1e-4, 1), eps, 1 - eps) with a straight-through inner clamp (the arithmetic of
 // render.hip pn_zero_one_value / k_zero_one_backward_rays), times the caller's scale
@@ -299,6 +307,10 @@ constexpr int BL_ROW = PN_XBYTES, BL_W5 = BL_ROW + 7 * PN_TILE * 4, BL_BYTES = B
 constexpr int LDDX = 228;                      // fp32 row stride of the d X0 tile (over the activation tile's space)
 static_assert(2 * BL_BYTES <= 160 * 1024, "two backward workgroups must fit the 160 KB LDS");
 static_assert(PN_TILE * LDDX * 4 <= PN_XBYTES, "d X0 tile");
+// xyz_grad (XYZG): the d X0 tile holds all 288 columns, and the rows' d(w = wn conf) (scaled) sit behind the alpha head's weights
+constexpr int LDDX_X = 292, BL_GW = BL_BYTES, BL_BYTES_X = BL_GW + PN_TILE * 4;
+static_assert(2 * BL_BYTES_X <= 160 * 1024, "two xyz_grad backward workgroups must fit the 160 KB LDS");
+static_assert(PN_TILE * LDDX_X * 4 <= PN_XBYTES, "d X0 tile (xyz_grad)");
 
 template <int N> __device__ __forceinline__ float group_sum_b(float v) {
 #pragma unroll
@@ -370,10 +382,11 @@ __device__ __forceinline__ float pn_sigmoid_b(float x) {
 // samples, whose d f values come straight from memory like KC = 2, 1); the two-pass form it replaces read the tile twice with a barrier between.
 // MIX: dY4 leaves in the mixed format of mixq.h: h (nearest f16) in plane 0 and, in place of the thread's 16 bytes of the h4 residual plane, the
 // group's e4m3 unit [q8(h) x 8 | q8(m 2^11) x 8] -- a thread still rewrites only bytes it alone reads
-template <int KC, bool MIX = false>
+// XG (xyz_grad): the row's d w (d sigma alpha + d f . h4, scaled; 0 for a row without a point) also goes to gwf[row] for the weight chain
+template <int KC, bool MIX = false, bool XG = false>
 __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *w5s, const float *wrow, const float *wnrm, const float *dsg, const float *xrow,
                                         float *draw, const int *sidx, const int *prow, const float4 (&dfr)[4], const float *dfb0, float S, float invS, int tid,
-                                        float (&gw5)[8], float &gb5t, unsigned kinv = 0u) {
+                                        float (&gw5)[8], float &gb5t, unsigned kinv = 0u, float *gwf = nullptr) {
     const int lane = tid & 63, cg = tid & 31, r0 = 8 * (tid >> 5);
     const int j0 = KC == 0 ? pn_row_div(r0, kinv) : 0;
     // (zero-one regulariser riding on the conf atomic below: the row's confidence, requested now, used behind the butterfly)
@@ -412,16 +425,18 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
         pd[0] += __shfl_xor(pd[0], 1, 64);
         const int r = r0 + ((lane >> 4) & 1) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 2) & 1);
         if ((lane & 3) == 0) {
-            float dr = 0.f;
+            float dr = 0.f, gw = 0.f;
             if (sidx[r] >= 0) {
                 const float x = xrow[r], dotf = pd[0] * S;
                 const float alpha = pn_softplus_b(x), sg = pn_sigmoid_b(x);
                 const int rp = prow[r];
                 // w = wn * clamp(conf) with a straight-through clamp (gradiant_clamp, point_aggregators.py:722-724)
                 if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * invS + (a.zo_gs ? pn_zero_one_grad(zo_conf, a.zo_eps, a.zo_gs[0]) : 0.f));
+                if (XG && rp >= 0) gw = dsg[r] * alpha + dotf;
                 dr = dsg[r] * wrow[r] * sg;
             }
             draw[r] = dr;
+            if (XG) gwf[r] = gw;
         }
     }
     PN_WAVE_LDS_SYNC();
@@ -458,13 +473,75 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
     if (cg == 0) gb5t += drsum;
 }
 
+// ---- xyz_grad: the row's d xyz, on the four threads (row, q) of the row-wise phase (adjacent lanes; every lane of the wave calls this).
+// The specification is the reference's autograd through the distance features and the inverse-distance weights (point_aggregators.py:425-428,
+// :773-781, :801-811; oracle/pyref.py aggregate):
+//   X0 columns 224 + 10 c + 2 f, + 1 = sin, cos (2^f d_c),  d = [Rw2c dw | pc - sc],  dw = xyz[p] - loc  (pc, sc: camera coordinates of the
+//   point and of the sample; d3, d4 are (pcx / pcz) pcz - (scx / scz) scz: exactly pc - sc, differentiated as such)
+//   w = wn clamp(conf),  wn = wraw / sum_k wraw_k,  wraw = 1 / max(|dw|, 1e-6)
+// ->  d xyz = Rw2c^T d d[0:3] + camrot d d[3:6] - wraw^2 (d w  w - T wn) dw   (the last term 0 where the clamp holds), T = sum over the
+// sample's rows of d w_k w_k.  The distances are recomputed in fp32 from xyz / sample_loc / camera as the forward forms them (the saved f16
+// plane of X0 has too few bits for a derivative); dxr (the row's d X0) and gwf (d w) carry the call's scale S.  Thread q takes the components
+// q and q + 4 (the forward's split) and a quarter of T; three atomics per row.
+__device__ __forceinline__ void b_xyz_row(const BwdXArgs &a, const float *dxr, const float *gwf, const float *wrow, const float *wnrm, const int *sidx,
+                                          int rp, int row, int q, int K, unsigned kinv, float invS) {
+    float u[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, t = 0.f;
+    float dwx = 0.f, dwy = 0.f, dwz = 0.f;
+    if (rp >= 0) {
+        const long long si = sidx[row];
+        const float px = a.xyz[3 * rp], py = a.xyz[3 * rp + 1], pz = a.xyz[3 * rp + 2];
+        const float lx = a.sample_loc[si * 3], ly = a.sample_loc[si * 3 + 1], lz = a.sample_loc[si * 3 + 2];
+        dwx = px - lx; dwy = py - ly; dwz = pz - lz;
+        float pcx, pcy, pcz, scx, scy, scz, d0, d1, d2;
+        rot3b(a.cam.camrot, px - a.cam.campos[0], py - a.cam.campos[1], pz - a.cam.campos[2], false, pcx, pcy, pcz);
+        rot3b(a.cam.camrot, lx - a.cam.campos[0], ly - a.cam.campos[1], lz - a.cam.campos[2], false, scx, scy, scz);
+        rot3b(a.cam.rw2c, dwx, dwy, dwz, true, d0, d1, d2);
+        const float d3 = (pcx / pcz) * pcz - (scx / scz) * scz, d4 = (pcy / pcz) * pcz - (scy / scz) * scz, d5 = pcz - scz;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c = q + 4 * j;
+            if (c < 6) {
+                float sn[5], cs[5];
+                pn_pe_octaves<5>(j == 0 ? (q == 0 ? d0 : q == 1 ? d1 : q == 2 ? d2 : d3) : (q == 0 ? d4 : d5), sn, cs);
+                float g = 0.f, fr = 1.f;
+#pragma unroll
+                for (int f = 0; f < 5; ++f) {
+                    const float2 x = *reinterpret_cast<const float2 *>(dxr + PN_F * 7 + (c * 5 + f) * 2);
+                    g += fr * (x.x * cs[f] - x.y * sn[f]);
+                    fr *= 2.f;
+                }
+#pragma unroll
+                for (int i = 0; i < 6; ++i) u[i] = c == i ? g : u[i];
+            }
+        }
+        const int k0 = pn_row_div(row, kinv) * K;
+        for (int k = q; k < K; k += 4) t += gwf[k0 + k] * wrow[k0 + k];
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) u[i] = group_sum_b<4>(u[i]);
+    t = group_sum_b<4>(t);
+    if (rp >= 0 && q < 3) {
+        float gx, gy, gz, hx, hy, hz;
+        rot3b(a.cam.rw2c, u[0], u[1], u[2], false, gx, gy, gz);
+        rot3b(a.cam.camrot, u[3], u[4], u[5], true, hx, hy, hz);
+        const float len = sqrtf(dwx * dwx + dwy * dwy + dwz * dwz);
+        const float cw = len >= 1e-6f ? -(gwf[row] * wrow[row] - t * wnrm[row]) / (len * len) : 0.f;
+        const float v = q == 0 ? gx + hx + cw * dwx : q == 1 ? gy + hy + cw * dwy : gz + hz + cw * dwz;
+        atomicAdd(&a.g_xyz[3 * rp + q], v * invS);
+    }
+}
+
 #ifdef PN_PHASE_TRACE
 PN_TR_DECL(pn_trace_bwd);
 #endif
 // MIX: the four input-gradient GEMMs in the mixed format of mixq.h (f16 h.h + e4m3 cross terms; the default since round 6)
-template <bool WG2, bool MIX = false>
-__global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) {
+// XYZG (xyz_grad, a.g_xyz): the layer-1 dgrad also forms d X0 columns 224 .. 287 (two more feature blocks, image PKH_D1T / PKM_D1T, on the
+// fourth wave, whose share of the seven blocks is one), and a row-wise phase behind the embedding gradient carries them and the inverse-distance
+// weights back to the point positions (b_xyz_row).  4-wave organisation only (the launcher refuses the other).
+template <bool WG2, bool MIX = false, bool XYZG = false>
+__global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename BwdArgsOf<XYZG>::T a) {
     static_assert(!(MIX && WG2), "the two-plane weight-gradient mode keeps f16x3.h's arithmetic everywhere");
+    constexpr int LDX = XYZG ? LDDX_X : LDDX;
     pn_mode_saturate();
     extern __shared__ __attribute__((aligned(16))) char smem_b[];
     char *X = smem_b;
@@ -472,6 +549,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) 
     int *sidx = reinterpret_cast<int *>(xrow + PN_TILE), *prow = sidx + PN_TILE;
     float *w5s = reinterpret_cast<float *>(smem_b + BL_W5);
     float *dx = reinterpret_cast<float *>(smem_b);
+    float *gwf = XYZG ? reinterpret_cast<float *>(smem_b + BL_GW) : nullptr;
     const int tid0 = threadIdx.x;
     const int K = a.K, TS = a.TS;
     const unsigned kinv = pn_kinv(K);
@@ -576,11 +654,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) 
         {
             // ---- alpha head backward + dY4 in one pass (b_front): K = 8 / 4 / 2 / 1 with compile-time sample boundaries, any other K at run time
             if (!ew) { PN_EMU_MATCH_WAVE_SYNC(); }
-            else if (K == 8) b_front<8, MIX>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t);
-            else if (K == 4) b_front<4, MIX>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t);
-            else if (K == 2) b_front<2, MIX>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t);
-            else if (K == 1) b_front<1, MIX>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t);
-            else b_front<0, MIX>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, kinv);
+            else if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 4) b_front<4, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 2) b_front<2, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 1) b_front<1, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
+            else b_front<0, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, kinv, gwf);
             PN_TR(pn_trace_bwd, 2);
         }
         // (round 4: the first weight-fragment chunks of every GEMM are requested in FRONT of the barrier that precedes it -- see the forward)
@@ -687,19 +765,37 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) 
         b_epilogue<MIX>(acc, m1, X, wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 12);
-        // ---- layer 1: dY1 -> d X0 (columns 0..223), fp32 into LDS
+        // ---- layer 1: dY1 -> d X0 (columns 0..223; XYZG: 0..287), fp32 into LDS
         b_acc_zero(acc);
         PN_TR(pn_trace_bwd, 13);
+        // XYZG, wave 3: d X0 columns 224 .. 255 into its idle second accumulator block, 256 .. 287 into acx (two passes of one block each:
+        // one pass of two would hold a third block of accumulators at once)
+        [[maybe_unused]] f32x16 acx[1][2];
+        [[maybe_unused]] f32x16 (&acc1)[1][2] = *reinterpret_cast<f32x16 (*)[1][2]>(&acc[PN_NFB - 1]);
         if constexpr (MIX) {
             if (PN_NFB == 2) {
                 if (wave < 3) pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, PN_NFB>(X, img + PKM_D1, 2 * wave, lane, acc);
-                else pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, 6, lane, acc);
+                else {
+                    pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, 6, lane, acc);
+                    if constexpr (XYZG) {
+                        pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 0, lane, acc1);
+                        b_acc_zero(acx);
+                        pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 1, lane, acx);
+                    }
+                }
             } else if (wave < PN_MB_D1) {
                 pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, wave, lane, acc);
             }
-        } else if (PN_NFB == 2) {       // seven feature blocks over four waves: 2 2 2 1
+        } else if (PN_NFB == 2) {       // seven feature blocks over four waves: 2 2 2 1 (XYZG: 2 2 2 3)
             if (wave < 3) pn_gemm_f16x3<16, PN_MB_D1, PN_NFB>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), 2 * wave, lane, acc);
-            else pn_gemm_f16x3<16, PN_MB_D1, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), 6, lane, acc);
+            else {
+                pn_gemm_f16x3<16, PN_MB_D1, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), 6, lane, acc);
+                if constexpr (XYZG) {
+                    pn_gemm_f16x3<16, 2, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1T), 0, lane, acc1);
+                    b_acc_zero(acx);
+                    pn_gemm_f16x3<16, 2, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1T), 1, lane, acx);
+                }
+            }
         } else if (wave < PN_MB_D1) {      // over eight waves: one each, the last wave idle
             pn_gemm_f16x3<16, PN_MB_D1, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), wave, lane, acc);
         }
@@ -714,9 +810,23 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) 
                 for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<float4 *>(dx + (32 * rb + (lane & 31)) * LDDX + pn_d_feat(PN_NFB * wave + fb, g, lane)) =
+                        *reinterpret_cast<float4 *>(dx + (32 * rb + (lane & 31)) * LDX + pn_d_feat(PN_NFB * wave + fb, g, lane)) =
                             make_float4(acc[fb][rb][4 * g], acc[fb][rb][4 * g + 1], acc[fb][rb][4 * g + 2], acc[fb][rb][4 * g + 3]);
             }
+        if constexpr (XYZG && PN_NFB == 2) {
+            if (wave == 3) {
+#pragma unroll
+                for (int fb = 0; fb < 2; ++fb)
+#pragma unroll
+                    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            const f32x16 &v = fb == 0 ? acc1[0][rb] : acx[0][rb];
+                            *reinterpret_cast<float4 *>(dx + (32 * rb + (lane & 31)) * LDX + pn_d_feat(PN_MB_D1 + fb, g, lane)) =
+                                make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+                        }
+            }
+        }
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 15);
         // ---- embedding gradient through [e | PE3(e)]: d e = dX[e] + sum_f 2^f (dX[sin_f] cos_f - dX[cos_f] sin_f)
@@ -726,7 +836,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) 
         // row's own d X0 columns (which only their thread reads), and the wave -- it holds 16 whole rows -- sends them out two rows per
         // instruction: lanes 0..31 = the 128-byte gradient row of one point, lanes 32..63 the next row's.
         if (bw && rp >= 0) {
-            float *dr_ = dx + row * LDDX;
+            float *dr_ = dx + row * LDX;
             const float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
             float go[EPT];
 #pragma unroll
@@ -752,8 +862,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(BwdArgs a) 
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int r = r0w + 2 * j, p = prow[r];
-                if (p >= 0) atomicAdd(&a.g_emb[(long long)p * PN_F + col], dx[r * LDDX + col]);
+                if (p >= 0) atomicAdd(&a.g_emb[(long long)p * PN_F + col], dx[r * LDX + col]);
             }
+        }
+        if constexpr (XYZG) {
+            if (bw) b_xyz_row(a, dx + row * LDX, gwf, wrow, wnrm, sidx, rp, row, q, K, kinv, invS);
         }
         PN_TR(pn_trace_bwd, 16);
     }
@@ -1285,17 +1398,24 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     a.conf = pts->conf; a.zo_gs = x0_saved ? nullptr : pg->zero_one_gscale; a.zo_eps = pg->zero_one_eps;       // (the fused render path only)
     if (a.zo_gs && !a.conf) return PNERF_E_INVAL;
     if (!a.g_emb || !a.g_conf || !a.g_dir || !a.g_color) return PNERF_E_INVAL;
+    // xyz_grad: the fused render path (world-coordinate distances recomputed from xyz / sample_loc), 4-wave organisation
+    BwdXArgs ax;
+    ax.xyz = pts->xyz; ax.sample_loc = d_sample_loc; ax.g_xyz = pg->xyz;
+    const bool xg = ax.g_xyz != nullptr;
+    if (xg && (x0_saved || PN_NFB != 2)) return PNERF_E_UNSUP;
+    if (xg && (!ax.xyz || !ax.sample_loc)) return PNERF_E_INVAL;
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) != hipSuccess) return PNERF_E_LAUNCH;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 256;
     const long long ctiles = (n_valid + PN_CTILE - 1) / PN_CTILE;
     const int grid_c = (int)(ctiles < 3 * ncu ? (ctiles > 0 ? ctiles : 1) : 3 * ncu);       // 40 KB of LDS: three workgroups per CU
-    const size_t lds_c = CB_BYTES, lds_a = BL_BYTES;
+    const size_t lds_c = CB_BYTES, lds_a = xg ? BL_BYTES_X : BL_BYTES;
     const bool wg2 = sv.wg2 != 0;                      // two-plane weight-gradient mode (the forward of this step ran in it: same process-wide setting)
     if (wg2) x0_saved = true;
     const void *kcb = wg2 ? (const void *)k_color_backward<true> : (const void *)k_color_backward<false>;
     const bool mix = !wg2 && (pn_mix_mask() & 4);      // mixq.h: e4m3 cross terms in the input-gradient chain
-    const void *kab = wg2 ? (const void *)k_agg_backward<true> : mix ? (const void *)k_agg_backward<false, true> : (const void *)k_agg_backward<false>;
+    const void *kab = xg ? (wg2 ? (const void *)k_agg_backward<true, false, true> : mix ? (const void *)k_agg_backward<false, true, true> : (const void *)k_agg_backward<false, false, true>)
+                         : (wg2 ? (const void *)k_agg_backward<true> : mix ? (const void *)k_agg_backward<false, true> : (const void *)k_agg_backward<false>);
     if (hipFuncSetAttribute(kcb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
     if (hipFuncSetAttribute(kab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
     // the forward left the class partition of the valid samples in the saved area (aggregate.hip: pn_classify)
@@ -1317,7 +1437,11 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
           a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
           const long long tiles = (n_valid + a.TS - 1) / a.TS;                    // worst-case grid, two workgroups per CU
           const int grid_a = (int)(tiles < 2LL * ncu ? (tiles > 0 ? tiles : 1) : 2LL * ncu);
-          if (wg2) hipLaunchKernelGGL(k_agg_backward<true>, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
+          if (xg) static_cast<BwdArgs &>(ax) = a;
+          if (xg && wg2) hipLaunchKernelGGL((k_agg_backward<true, false, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax);
+          else if (xg && mix) hipLaunchKernelGGL((k_agg_backward<false, true, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax);
+          else if (xg) hipLaunchKernelGGL((k_agg_backward<false, false, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax);
+          else if (wg2) hipLaunchKernelGGL(k_agg_backward<true>, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
           else if (mix) hipLaunchKernelGGL((k_agg_backward<false, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
           else hipLaunchKernelGGL(k_agg_backward<false>, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
       } }

@@ -52,6 +52,9 @@ enum : int {
     PKM_D4 = PKM_F4 + PN_MIMG(0, 8), PKM_D3 = PKM_D4 + PN_MIMG(0, 8), PKM_D2 = PKM_D3 + PN_MIMG(0, 9), PKM_D1 = PKM_D2 + PN_MIMG(0, 8),
     PKM_END = PKM_D1 + PN_MIMG(0, PN_MB_D1)
 };
+// xyz_grad (k_agg_backward<.., XYZG>): the two feature blocks of d X0 behind the seven above, columns 224 .. 287 (the distance encoding), as
+// W1^T rows 224 .. 287 in either arithmetic.  Placed behind every other image so that no offset the other kernels use moves.
+enum : int { PKH_D1T = PKM_END, PKM_D1T = PKH_D1T + PN_IMG(16, 2), PKX_END = PKM_D1T + PN_MIMG(0, 2) };
 
 // MODE.FP16_OVFL = 1: f16 and fp8 conversions saturate instead of producing inf / NaN (per wave; every wave of a tile kernel runs this first)
 __device__ __forceinline__ void pn_mode_saturate() {

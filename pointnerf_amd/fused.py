@@ -3,9 +3,10 @@ torch.autograd.Function over the C-ABI library (no per-stage tensors cross the P
 
 This is what ``NeuralPointsRayMarching.forward`` (pointnerf_amd/neural_points_volumetric_model.py) runs; it
 replaces the reference's ``neural_points(...) -> aggregator(...) -> ray_dist -> ray_march`` chain
-(models/neural_points_volumetric_model.py:268-306).  Autograd sees four leaves: the flat MLP parameter vector and
-the per-point tensors (embedding, conf, dir, colour); xyz gets no gradient (``xyz_grad=0`` in every reference
-script, lego_cuda.sh: default of --xyz_grad in neural_points.py:132).
+(models/neural_points_volumetric_model.py:268-306).  Autograd sees the flat MLP parameter vector and the per-point tensors
+(embedding, conf, dir, colour); the point positions are a fifth point leaf only when they require grad (``--xyz_grad 1``,
+neural_points.py:132; every reference script leaves it 0): the backward then also forms d xyz through the distance encoding and the
+inverse-distance weights (k_agg_backward's XYZG instances), and returns it in the same point-gradient bucket.
 """
 import torch
 
@@ -29,8 +30,9 @@ class MLPState:
 
 
 class FusedRender(torch.autograd.Function):
-    """apply(env, emb, conf, dir, color, *mlp_params) -> (ray_color [R,3], opacity [R,SR], bg_trans [R],
-    blend_w [R,SR], decoded [R,SR,4], weight [R,SR,K]); only ray_color carries gradient.
+    """apply(env, emb, conf, dir, color[, xyz], *mlp_params) -> (ray_color [R,3], opacity [R,SR], bg_trans [R],
+    blend_w [R,SR], decoded [R,SR,4], weight [R,SR,K]); only ray_color carries gradient.  ``xyz`` (the point positions, the tensor
+    ``env['xyz']`` is a flat view of) is passed only when ``env['xyz_grad']``: it then receives d xyz.
 
     ``mlp_params`` are the aggregator's nn.Parameters in ``pnerf_mlp_layout`` order; they are views of the flat
     vector ``env['flat']`` the kernels read, and are passed only so that autograd (and DDP-style hooks) see them:
@@ -46,7 +48,11 @@ class FusedRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, env, emb, conf, pdir, color, *mlp_params):
-        # env: dict(cam, xyz, raydir, dense, R, SR, K, n_valid, flat, packed, train, layout)
+        # env: dict(cam, xyz, raydir, dense, R, SR, K, n_valid, flat, packed, train, layout[, xyz_grad])
+        ctx.xyz_shape = None
+        if env.get("xyz_grad"):
+            ctx.xyz_shape = tuple(mlp_params[0].shape)
+            mlp_params = mlp_params[1:]
         # (the C structure holds raw pointers: keep the arrays it points to alive until the backward has read them)
         ctx.point_arrays = (emb.detach().reshape(-1, emb.shape[-1]), conf.detach().reshape(-1, 1), pdir.detach().reshape(-1, 3),
                             color.detach().reshape(-1, 3))
@@ -100,17 +106,21 @@ class FusedRender(torch.autograd.Function):
         FusedRender.last_chunks = None
         gflat = torch.zeros_like(env["flat"])
         names = ("points_embeding", "points_conf", "points_dir", "points_color")
-        # ONE zero-filled bucket for the four point-gradient tensors, [embedding | dir | colour | conf]: the three tensors that are final
+        shapes = ctx.shapes
+        # ONE zero-filled bucket for the four point-gradient tensors, [embedding | dir | colour | conf (| xyz)]: the three tensors that are final
         # at the library's ready event are contiguous at its head, so a data-parallel caller reduces them with one collective
-        # (dist.allreduce_grads); the four gradients autograd receives are views of it
+        # (dist.allreduce_grads); the four gradients autograd receives are views of it.  xyz_grad: d xyz at the tail (reduced with the other
+        # point tensors by dist.allreduce_grads' per-tensor path)
         order = (0, 2, 3, 1)
-        sizes = [int(torch.Size(shp).numel()) for shp in ctx.shapes]
+        if ctx.xyz_shape is not None:
+            names, shapes, order = names + ("xyz",), shapes + (ctx.xyz_shape,), order + (4,)
+        sizes = [int(torch.Size(shp).numel()) for shp in shapes]
         offs, o = {}, 0
         for i in order:
             offs[i] = o
             o += (sizes[i] + 3) // 4 * 4                # every view starts on a 16-byte boundary
         bucket = torch.zeros(o, dtype=torch.float32, device=dev)
-        grads = {n: bucket[offs[i]:offs[i] + sizes[i]].view(ctx.shapes[i]) for i, n in enumerate(names)}
+        grads = {n: bucket[offs[i]:offs[i] + sizes[i]].view(shapes[i]) for i, n in enumerate(names)}
         ev = None
         if env.get("want_grad_event"):            # data-parallel training: see pnerf_point_grads.ready_event
             ev = torch.cuda.Event()
@@ -141,7 +151,8 @@ class FusedRender(torch.autograd.Function):
         # the graph node outlives this call for as long as the caller keeps the loss: release the step's big tensors (query
         # outputs, dense weights, packed points) now, so that the next step's allocations find them in the allocator's cache
         ctx.env = ctx.fwd = ctx.pts = ctx.point_arrays = None
-        return (None, grads["points_embeding"], grads["points_conf"], grads["points_dir"], grads["points_color"]) + gm
+        gx = (grads["xyz"],) if "xyz" in grads else ()
+        return (None, grads["points_embeding"], grads["points_conf"], grads["points_dir"], grads["points_color"]) + gx + gm
 
 
 def _backward_in_chunks(env, pts, g_color, gflat, grads, ev):

@@ -32,6 +32,7 @@ class NeuralPoints(nn.Module):
             get = lambda k: saved["neural_points." + k] if ("neural_points." + k) in saved else None
             self.xyz = nn.Parameter(get("xyz").to(device))
             self.xyz.requires_grad = opt.xyz_grad > 0
+            self.xyz.pnerf_point_xyz = True
             for name, flag in (("points_embeding", "feat_grad"), ("points_conf", "conf_grad"), ("points_dir", "dir_grad"),
                                ("points_color", "color_grad")):
                 t = get(name)
@@ -68,6 +69,8 @@ class NeuralPoints(nn.Module):
     def _param(self, t, flag):
         p = nn.Parameter(t)
         p.requires_grad = getattr(self.opt, flag) > 0
+        if flag == "xyz_grad":
+            p.pnerf_point_xyz = True          # (optim.ShardedAdam refuses trainable positions: see there)
         return p
 
     def prune(self, thresh):

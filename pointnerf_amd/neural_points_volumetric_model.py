@@ -68,9 +68,8 @@ class NeuralPointsRayMarching(nn.Module):
         the zero-one regulariser's numerator over the hit rays' conf_coefficient when ``_zero_one_in_render()`` (else a constant 0)."""
         opt, npnt, agg = self.opt, self.neural_points, self.aggregator
         train = torch.is_grad_enabled() if train is None else train
-        if train and getattr(opt, "xyz_grad", 0) > 0:
-            raise NotImplementedError("xyz_grad > 0 (optimising point positions) is not on any reference script's path and the "
-                                      "fused backward produces no d/d xyz")
+        # xyz_grad > 0: the point positions are a leaf of the fused step (d xyz from k_agg_backward's XYZG instances)
+        xyz_leaf = bool(train) and npnt.xyz.requires_grad
         R = raydir.reshape(-1, 3).shape[0]
         if train and self._pool_rays < R:              # worst case (every ray hits): ~16 live [R,SR,K] fp32 tensors around the loss
             ops.reserve_pool(16 * R * int(opt.SR) * int(opt.K) * 4, raydir.device)
@@ -79,6 +78,9 @@ class NeuralPointsRayMarching(nn.Module):
         # data-parallel callers that exchange touched rows only (dist.plan_sparse_exchange) prepare the row list here, so that its two
         # counts travel with the one host read below instead of synchronising a second time after the backward
         plan = getattr(self, "plan_sparse", None)
+        if plan is not None and xyz_leaf:
+            raise NotImplementedError("xyz_grad > 0 with the sparse-row gradient exchange (dist.plan_sparse_exchange): the point positions' "
+                                      "gradient is not part of the touched-row exchange; use the dense all-reduce (dist.allreduce_grads)")
         plan = plan(dense) if (plan is not None and train) else None
         words = dense["counters"].to(torch.int64) if plan is None else torch.cat([dense["counters"].to(torch.int64), plan[1]])
         st = agg.mlp_state()
@@ -92,7 +94,9 @@ class NeuralPointsRayMarching(nn.Module):
                    train=bool(train), layout=layout, want_grad_event=bool(train) and raydir.is_cuda and pdist.active())
         if train and self._zero_one_in_render():
             env["zero_one_eps"] = float(getattr(opt, "zero_epsilon", 1e-3))
-        leaves = (npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + tuple(mlp_params)
+        if xyz_leaf:
+            env["xyz_grad"] = True
+        leaves = (npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + ((npnt.xyz,) if xyz_leaf else ()) + tuple(mlp_params)
         # The step's one host read (number of valid samples: sizes the activation arena; number of hit rays: shapes of the outputs).
         # Round 4: a TRAINING step whose arena already exists is enqueued BEFORE that read with the arena's capacity as the bound -- every
         # kernel takes the actual counts from the device (`counters`, the class partition's tile counts), the host number is only "how much

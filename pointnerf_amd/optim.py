@@ -64,6 +64,11 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 st["step"] += 1
+                if getattr(p, "pnerf_point_xyz", False):
+                    # xyz_grad: the update writes the point positions through a raw pointer (no version bump), so the voxel-grid cache
+                    # (point_query: keyed by address and version) would keep matching the OLD cloud -- drop it; the next query rebuilds
+                    from . import point_query
+                    point_query.clear_grid_cache()
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 batches.setdefault((float(b1), float(b2), float(group["eps"])), []).append(
                     (p.data, g, st["exp_avg"], st["exp_avg_sq"], float(group["lr"]), int(st["step"].item())))
@@ -111,6 +116,11 @@ class ShardedAdam:
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, group=None, update=None):
         self.params = [p for p in params]
+        if any(getattr(p, "pnerf_point_xyz", False) and p.requires_grad for p in self.params):
+            # its all-gather rewrites the positions in place without a version bump (the voxel-grid cache would keep the old cloud), and the
+            # re-homing moves them on every re-construction: not supported
+            raise NotImplementedError("xyz_grad > 0: ShardedAdam (ZeRO-1) does not take the point positions; step them with FusedAdam "
+                                      "(dense all-reduce, dist.allreduce_grads) instead")
         self.lr, self.betas, self.eps, self.group = lr, betas, eps, group
         self._update = update or _adam_hip
         self.step_count = 0
