@@ -596,7 +596,6 @@ __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char
             pn_x_store2(X, row, PN_F + dd * 6 + 2, s[1], c[1]);
             pn_x_store2(X, row, PN_F + dd * 6 + 4, s[2], c[2]);
         }
-        if (PN_NW == 8 && (i & 1)) __builtin_amdgcn_sched_barrier(0);      // (register budget of the 8-wave organisation)
     }
     }
     // PE5 of distance components q and q + 4
@@ -739,8 +738,6 @@ __device__ __forceinline__ void f_tail(const FwdArgs &a, const char *X, const fl
             f0.x = pn_fma2_lo(h.x, m.x, w, f0.x); f0.y = pn_fma2_hi(h.x, m.x, w, f0.y); f0.z = pn_fma2_lo(h.y, m.y, w, f0.z); f0.w = pn_fma2_hi(h.y, m.y, w, f0.w);
             f1.x = pn_fma2_lo(h.z, m.z, w, f1.x); f1.y = pn_fma2_hi(h.z, m.z, w, f1.y); f1.z = pn_fma2_lo(h.w, m.w, w, f1.z); f1.w = pn_fma2_hi(h.w, m.w, w, f1.w);
         }
-        // 128 registers per wave in the 8-wave organisation: at most two rows' planes in flight (the scheduler otherwise hoists all 16 reads)
-        if (PN_NW == 8 && (i & 1)) __builtin_amdgcn_sched_barrier(0);
     }
     // f rows of the thread's samples (class-ordered list: the colour MLP reads them in that order)
 #pragma unroll
@@ -812,26 +809,17 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
     const char *img = reinterpret_cast<const char *>(a.packed);
     if (tid0 < PN_H) w5s[tid0] = P[PO_W5 + tid0];
     const float b5 = P[PO_B5];
-    // tiles of a workgroup: blockIdx.x, blockIdx.x + gridDim.x, ... (the chip works on one moving window of the saved area);
-    // dev A/B -DPN_TILE_BLOCKED: one contiguous run of tiles per workgroup (consecutive tiles = consecutive samples of a ray on ONE CU)
-#ifdef PN_TILE_BLOCKED
-    const long long per_wg = (ntiles + gridDim.x - 1) / gridDim.x, stride = 1, tile_first = blockIdx.x * per_wg;
-    const long long tile_last = tile_first + per_wg < ntiles ? tile_first + per_wg : ntiles;
-#else
+    // tiles of a workgroup: blockIdx.x, blockIdx.x + gridDim.x, ... (the chip works on one moving window of the saved area; one contiguous
+    // run of tiles per workgroup measured the same, 12.85 against 12.90 ms)
     const long long stride = gridDim.x, tile_first = blockIdx.x, tile_last = ntiles;
-#endif
     if (tile_first >= tile_last) return;
 
-    // index pipeline of this thread's row: (si0, p0) current tile, (si1, p1) next, si2 the one after
+    // index pipeline of this thread's row (4 threads per tile row): (si0, p0) current tile, (si1, p1) next, si2 the one after
     long long tile = tile_first;
     int si0, si1, si2, p0, p1;
     FGather G;
-    // Roles in the 8-wave organisation: the LAST PN_ETHR threads (waves 4..7) own the gather + feature build + row weights (4 threads per
-    // tile row), the FIRST PN_ETHR threads (waves 0..3) own the tail.  The next tile's gathered point data is in flight across the tail:
-    // with both roles on the same waves it does not fit 128 registers beside the tail's rows (the compiler spilled it, i.e. waited for it).
-    si0 = si1 = si2 = p0 = p1 = -1;
-    if (tid0 >= PN_NTHR - PN_ETHR) {
-        const int bt = tid0 - (PN_NTHR - PN_ETHR), row = bt / TPR, q = bt % TPR, k = row - pn_row_div(row, kinv) * K;
+    {
+        const int row = tid0 / TPR, q = tid0 % TPR, k = row - pn_row_div(row, kinv) * K;
         si0 = f_sample_of(a, tile, row, Ns, kinv); si1 = tile + stride < tile_last ? f_sample_of(a, tile + stride, row, Ns, kinv) : -1;
         si2 = tile + 2 * stride < tile_last ? f_sample_of(a, tile + 2 * stride, row, Ns, kinv) : -1;
         p0 = si0 >= 0 ? a.pidx[(long long)si0 * a.Kstride + k] : -1;
@@ -848,13 +836,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const bool ew = PN_NTHR == PN_ETHR || tid < PN_ETHR;               // this thread works in the tail
-        const bool bw = PN_NTHR == PN_ETHR || tid >= PN_NTHR - PN_ETHR;    // this thread works in the gather / feature build
-        const int bt = bw ? tid - (PN_NTHR - PN_ETHR) : 0, row = bt / TPR, q = bt % TPR, k = row - pn_row_div(row, kinv) * K;
+        const int row = tid / TPR, q = tid % TPR, k = row - pn_row_div(row, kinv) * K;
         const long long gtile = tb + tile;               // tile index inside the saved area
         PN_LDS_BARRIER();                                 // the previous tile's readers are done with X and the row arrays
         PN_TR(pn_trace_fwd, 0); PN_TR_HWID(pn_trace_fwd);
-        if (bw) f_build<PERS, MIX, HR>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
+        f_build<PERS, MIX, HR>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
         // Round 4: what the next GEMM needs from GLOBAL memory -- its bias (the accumulators' initial value) and its first weight-fragment
         // chunks -- is requested in front of the barrier that precedes it, not behind: neither depends on LDS, and the L2 round trip
         // (0.6 .. 1.1 us per layer in profiles/r03_phase_trace.json: the "acc = bias" phases) passes under the barrier wait.
@@ -864,7 +850,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         if constexpr (MIX) M1.prefetch(img + PKM_F1, PN_NFB * wave, lane);
         else W1.prefetch(reinterpret_cast<const uint4 *>(img + PKH_F1), PN_NFB * wave, lane);
         PN_LDS_BARRIER();
-        if (bw && q == 0) {      // weights of the row: normalise over the K slots, multiply by the clamped confidence (:801-811)
+        if (q == 0) {      // weights of the row: normalise over the K slots, multiply by the clamped confidence (:801-811)
             const int ls = pn_row_div(row, kinv);
             float wn = 0.f, w = 0.f;
             if (si0 >= 0) {
@@ -888,11 +874,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         else pn_gemm_f16x3_run<18, 8, PN_NFB, PN_WPF, NPC>(X, W1, lane, acc);
         if (TRAIN) {           // (behind the GEMM: see above)
             if (HC) {         // the tile's h plane IS the nearest f16: the k-major plane is its transpose
-                if (a.save_x0) pn_copy_out_kmajor_h<PN_NF1, PN_XRS, PN_NW>(X, a.sv.x0k, gtile * 8, tid);
-                else pn_copy_out_kmajor_cols64_h<224, PN_NW>(X, a.sv.x0k, gtile * 8, tid);
-            } else if (WG2) pn_copy_out_kmajor<PN_NF1, true, PN_NW>(X, a.sv.x0k, gtile * 8, tid, a.sv.x0m);
-            else if (a.save_x0) pn_copy_out_kmajor<PN_NF1, false, PN_NW>(X, a.sv.x0k, gtile * 8, tid);
-            else pn_copy_out_kmajor_cols64<224, PN_NW>(X, a.sv.x0k, gtile * 8, tid);       // the fused path: only the last 64 columns (k_wgrad_x0)
+                if (a.save_x0) pn_copy_out_kmajor_h<PN_NF1>(X, a.sv.x0k, gtile * 8, tid);
+                else pn_copy_out_kmajor_cols64_h<224>(X, a.sv.x0k, gtile * 8, tid);
+            } else if (WG2) pn_copy_out_kmajor<PN_NF1, true>(X, a.sv.x0k, gtile * 8, tid, a.sv.x0m);
+            else if (a.save_x0) pn_copy_out_kmajor<PN_NF1, false>(X, a.sv.x0k, gtile * 8, tid);
+            else pn_copy_out_kmajor_cols64<224>(X, a.sv.x0k, gtile * 8, tid);       // the fused path: only the last 64 columns (k_wgrad_x0)
         }
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 3);
@@ -910,8 +896,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M2, lane, acc);
         else pn_gemm_f16x3_run<16, 8, PN_NFB, PN_WPF, NPC>(X, W2, lane, acc);
         if (TRAIN) {      // (behind the GEMM: see below)
-            if (HC) pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X, a.sv.h1k, gtile * 8, tid);
-            else pn_copy_out_kmajor<PN_H, WG2, PN_NW>(X, a.sv.h1k, gtile * 8, tid, a.sv.h1m);
+            if (HC) pn_copy_out_kmajor_h<PN_H>(X, a.sv.h1k, gtile * 8, tid);
+            else pn_copy_out_kmajor<PN_H, WG2>(X, a.sv.h1k, gtile * 8, tid, a.sv.h1m);
         }
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 6);
@@ -943,8 +929,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 1, 8, PN_NFB>(X, M3, lane, acc);
         else pn_gemm_f16x3_run<17, 8, PN_NFB, PN_WPF, NPC>(X, W3, lane, acc);
         if (TRAIN) {      // (behind the GEMM: see below)
-            if (HC) pn_copy_out_kmajor_h<PN_NF1, PN_XRS, PN_NW>(X, a.sv.h2k, gtile * 8, tid);
-            else pn_copy_out_kmajor<PN_NF1, WG2, PN_NW>(X, a.sv.h2k, gtile * 8, tid, a.sv.h2m);
+            if (HC) pn_copy_out_kmajor_h<PN_NF1>(X, a.sv.h2k, gtile * 8, tid);
+            else pn_copy_out_kmajor<PN_NF1, WG2>(X, a.sv.h2k, gtile * 8, tid, a.sv.h2m);
         }
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 9);
@@ -962,8 +948,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M4, lane, acc);
         else pn_gemm_f16x3_run<16, 8, PN_NFB, PN_WPF, NPC>(X, W4, lane, acc);
         if (TRAIN) {
-            if (HC) pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X, a.sv.h3k, gtile * 8, tid);
-            else pn_copy_out_kmajor<PN_H, WG2, PN_NW>(X, a.sv.h3k, gtile * 8, tid, a.sv.h3m);
+            if (HC) pn_copy_out_kmajor_h<PN_H>(X, a.sv.h3k, gtile * 8, tid);
+            else pn_copy_out_kmajor<PN_H, WG2>(X, a.sv.h3k, gtile * 8, tid, a.sv.h3m);
         }
         PN_TR(pn_trace_fwd, 12);
         // the next tile's point data and the indices of the two after it: requested here, consumed at the top of the next
@@ -971,11 +957,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         const float cf_cur = G.cf;
         (void)cf_cur;
         const int si_next = si1, p_next = p1;
-        // (8 waves: the gather is issued by the build waves WHILE the tail waves run the tail, in the other arm of that branch -- then the
-        //  tail's code never holds the gathered registers)
-        if (PN_NW != 8 && tile + stride < tile_last) f_gather<PERS>(a, G, si1, p1, q);
+        if (tile + stride < tile_last) f_gather<PERS>(a, G, si1, p1, q);
         const int p2 = si2 >= 0 ? a.pidx[(long long)si2 * a.Kstride + k] : -1;
-        const int si3 = (bw && tile + 3 * stride < tile_last) ? f_sample_of(a, tile + 3 * stride, row, Ns, kinv) : -1;
+        const int si3 = tile + 3 * stride < tile_last ? f_sample_of(a, tile + 3 * stride, row, Ns, kinv) : -1;
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 13);
         f_epilogue<false>(acc, X, wave, lane, mask);
@@ -983,8 +967,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         PN_TR(pn_trace_fwd, 14);
         if (K == 8 || K == 4 || K == 2 || K == 1) {
             // ---- alpha head + h4 copy + K-weighted sums + sigma in one pass (f_tail)
-            if (!ew) { if (PN_NW == 8 && tile + stride < tile_last) f_gather<PERS>(a, G, si1, p1, q); }
-            else if (K == 8) f_tail<8, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid);
+            if (K == 8) f_tail<8, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid);
             else if (K == 4) f_tail<4, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid);
             else if (K == 2) f_tail<2, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid);
             else f_tail<1, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid);
@@ -992,8 +975,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         } else {
         // ---- (any other K: two passes) the per-row half in f_tail's mapping (alpha head 256 -> 1, softplus(x - 1), raw2out_density :262-265; h4 planes
         // streamed out for the backward), then the K-weighted sums
-        if (PN_NW == 8 && bw && tile + stride < tile_last) f_gather<PERS>(a, G, si1, p1, q);      // (8 waves: the build waves' prefetch, see above)
-        if (ew) f_tail<0, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid, wraw);
+        f_tail<0, TRAIN>(a, X, w5s, wrow, sidx, b5, tile, gtile, tid, wraw);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 15);
         // ---- K-weighted sums -> f[256] per sample (HBM), sigma
@@ -1261,15 +1243,17 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     const bool pers = d_xyz_pers != nullptr;
     const bool np2 = !train && pn_inference_products == 2;      // inference with the weights' high plane only (f16x3.h: NP)
     const bool mix = !wg2 && !np2 && (pn_mix_mask() & (train ? 2 : 1));      // mixq.h: f16 h.h + e4m3 cross terms
-    const void *kfn = wg2   ? (pers ? (const void *)k_agg_forward<true, true, 3, true> : (const void *)k_agg_forward<true, false, 3, true>)
-                    : mix   ? (train ? (pers ? (const void *)k_agg_forward<true, true, 4> : (const void *)k_agg_forward<true, false, 4>)
-                                     : (pers ? (const void *)k_agg_forward<false, true, 4> : (const void *)k_agg_forward<false, false, 4>))
-                    : train ? (pers ? (const void *)k_agg_forward<true, true, 3> : (const void *)k_agg_forward<true, false, 3>)
-                    : np2   ? (pers ? (const void *)k_agg_forward<false, true, 2> : (const void *)k_agg_forward<false, false, 2>)
-                            : (pers ? (const void *)k_agg_forward<false, true, 3> : (const void *)k_agg_forward<false, false, 3>);
-    const void *cfn = wg2 ? (const void *)k_color_forward<true, 3, true> : train ? (const void *)k_color_forward<true, 3> : np2 ? (const void *)k_color_forward<false, 2> : (const void *)k_color_forward<false, 3>;
-    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipFuncSetAttribute(cfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
+    // the one place that names the kernel instances: the selection serves both the LDS attribute and the launch
+    using FwdKernel = void (*)(FwdArgs);
+    const FwdKernel kfn = wg2   ? (pers ? k_agg_forward<true, true, 3, true> : k_agg_forward<true, false, 3, true>)
+                        : mix   ? (train ? (pers ? k_agg_forward<true, true, 4> : k_agg_forward<true, false, 4>)
+                                         : (pers ? k_agg_forward<false, true, 4> : k_agg_forward<false, false, 4>))
+                        : train ? (pers ? k_agg_forward<true, true, 3> : k_agg_forward<true, false, 3>)
+                        : np2   ? (pers ? k_agg_forward<false, true, 2> : k_agg_forward<false, false, 2>)
+                                : (pers ? k_agg_forward<false, true, 3> : k_agg_forward<false, false, 3>);
+    const FwdKernel cfn = wg2 ? k_color_forward<true, 3, true> : train ? k_color_forward<true, 3> : np2 ? k_color_forward<false, 2> : k_color_forward<false, 3>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(cfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
     int rc = pn_classify(sv, d_valid_list, d_counters, d_sample_pidx, K, cap_samples, train, save_x0, s);
     if (rc) return rc;
     a.cls_list = sv.cls_list; a.cls_info = sv.cls_info; a.Kstride = K;
@@ -1281,27 +1265,13 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
             a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
             const long long tiles = (cap_samples + a.TS - 1) / a.TS;
             const int grid_a = (int)(tiles < 2LL * ncu ? (tiles > 0 ? tiles : 1) : 2LL * ncu);     // two workgroups per CU
-            if (wg2 && pers) hipLaunchKernelGGL((k_agg_forward<true, true, 3, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (wg2) hipLaunchKernelGGL((k_agg_forward<true, false, 3, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (mix && train && pers) hipLaunchKernelGGL((k_agg_forward<true, true, 4>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (mix && train) hipLaunchKernelGGL((k_agg_forward<true, false, 4>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (mix && pers) hipLaunchKernelGGL((k_agg_forward<false, true, 4>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (mix) hipLaunchKernelGGL((k_agg_forward<false, false, 4>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (train && pers) hipLaunchKernelGGL((k_agg_forward<true, true, 3>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (train) hipLaunchKernelGGL((k_agg_forward<true, false, 3>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (np2 && pers) hipLaunchKernelGGL((k_agg_forward<false, true, 2>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (np2) hipLaunchKernelGGL((k_agg_forward<false, false, 2>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else if (pers) hipLaunchKernelGGL((k_agg_forward<false, true, 3>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-            else hipLaunchKernelGGL((k_agg_forward<false, false, 3>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
+            hipLaunchKernelGGL(kfn, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
         }
     }
     a.K = K; a.TS = pn_tile_samples(K); a.valid_list = sv.cls_list;      // the colour MLP walks the class-ordered list: f rows are in that order
     {
         PnProfScope prof(PNK_COLOR_FWD, s);
-        if (wg2) hipLaunchKernelGGL((k_color_forward<true, 3, true>), dim3(grid_c), dim3(256), lds_c, s, a);
-        else if (train) hipLaunchKernelGGL((k_color_forward<true, 3>), dim3(grid_c), dim3(256), lds_c, s, a);
-        else if (np2) hipLaunchKernelGGL((k_color_forward<false, 2>), dim3(grid_c), dim3(256), lds_c, s, a);
-        else hipLaunchKernelGGL((k_color_forward<false, 3>), dim3(grid_c), dim3(256), lds_c, s, a);
+        hipLaunchKernelGGL(cfn, dim3(grid_c), dim3(256), lds_c, s, a);
     }
     PN_CHECK_LAUNCH();
     return 0;

@@ -352,10 +352,8 @@ __device__ __forceinline__ void b_epilogue(const f32x16 (&acc)[PN_NFB][2], const
 // (The host emulation runs lanes as fibers: there it has to be a rendezvous.)
 #ifdef PN_EMU
 #define PN_WAVE_LDS_SYNC() __syncthreads()
-#define PN_EMU_MATCH_WAVE_SYNC() __syncthreads()      // for the threads of a workgroup that skip a phase with a PN_WAVE_LDS_SYNC in it
 #else
 #define PN_WAVE_LDS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define PN_EMU_MATCH_WAVE_SYNC() ((void)0)
 #endif
 __device__ __forceinline__ float pn_softplus_b(float x) {
 #ifdef PN_EMU
@@ -537,7 +535,7 @@ PN_TR_DECL(pn_trace_bwd);
 // MIX: the four input-gradient GEMMs in the mixed format of mixq.h (f16 h.h + e4m3 cross terms; the default since round 6)
 // XYZG (xyz_grad, a.g_xyz): the layer-1 dgrad also forms d X0 columns 224 .. 287 (two more feature blocks, image PKH_D1T / PKM_D1T, on the
 // fourth wave, whose share of the seven blocks is one), and a row-wise phase behind the embedding gradient carries them and the inverse-distance
-// weights back to the point positions (b_xyz_row).  4-wave organisation only (the launcher refuses the other).
+// weights back to the point positions (b_xyz_row).
 template <bool WG2, bool MIX = false, bool XYZG = false>
 __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename BwdArgsOf<XYZG>::T a) {
     static_assert(!(MIX && WG2), "the two-plane weight-gradient mode keeps f16x3.h's arithmetic everywhere");
@@ -567,12 +565,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
     f32x16 acc[PN_NFB][2];
     // row metadata of the tile (threads 0..63: one row each), fetched ONE TILE AHEAD: the d sigma of a row hangs off its sample id, and
     // two dependent HBM round trips at the top of every tile were 4 of the 6 us of the load phase
-#ifdef PN_TILE_BLOCKED       // (dev A/B: see the forward)
-    const long long per_wg = (ntiles + gridDim.x - 1) / gridDim.x, stride = 1, tile_first = blockIdx.x * per_wg;
-    const long long tile_last = tile_first + per_wg < ntiles ? tile_first + per_wg : ntiles;
-#else
     const long long stride = gridDim.x, tile_first = blockIdx.x, tile_last = ntiles;
-#endif
     int4 rm_cur = make_int4(-1, -1, 0, 0);
     float ar_cur = 0.f;
     if (tid0 < PN_TILE && tile_first < tile_last) {
@@ -585,10 +578,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         int tid = threadIdx.x;                          // (recomputed per tile: see the forward)
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        // roles in the 8-wave organisation (the forward's): the first PN_ETHR threads (waves 0..3) own the front (alpha head backward + dY4),
-        // the last PN_ETHR threads (waves 4..7) the rows' embedding gradients (4 threads per tile row: row, q)
-        const bool ew = PN_NTHR == PN_ETHR || tid < PN_ETHR, bw = PN_NTHR == PN_ETHR || tid >= PN_NTHR - PN_ETHR;
-        const int bt = bw ? tid - (PN_NTHR - PN_ETHR) : 0, row = bt / TPR, q = bt % TPR;
+        const int row = tid / TPR, q = tid % TPR;          // the row-wise phases: 4 threads per tile row
         const long long gtile = tb + tile;
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 0); PN_TR_HWID(pn_trace_bwd);
@@ -608,9 +598,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             const int r = rm_cur.x / a.SR;
             rdx = a.raydir[3 * r]; rdy = a.raydir[3 * r + 1]; rdz = a.raydir[3 * r + 2];
         }
-        pn_f4 h4v[4096 / PN_NTHR];
+        pn_f4 h4v[2 * PN_TILE * 32 / PN_NTHR];          // both planes of the tile's 64 x 256 h4, 16 bytes per unit
 #pragma unroll
-        for (int i = 0; i < 4096 / PN_NTHR; ++i) {
+        for (int i = 0; i < 2 * PN_TILE * 32 / PN_NTHR; ++i) {
             const int e = tid + PN_NTHR * i, plane = e >> 11, r = (e >> 5) & 63, u = e & 31;
             h4v[i] = *reinterpret_cast<const pn_f4 *>(a.sv.h4r + ((long long)plane * a.sv.rows + gtile * PN_TILE + r) * 32 + u);
         }
@@ -628,7 +618,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             dsg[tid] = dsg_v * S;
         }
 #pragma unroll
-        for (int i = 0; i < 4096 / PN_NTHR; ++i) {
+        for (int i = 0; i < 2 * PN_TILE * 32 / PN_NTHR; ++i) {
             const int e = tid + PN_NTHR * i, plane = e >> 11, r = (e >> 5) & 63, u = e & 31;
             *reinterpret_cast<pn_f4 *>(X + plane * PN_XPLANE + r * PN_XRS + u * 16) = h4v[i];
         }
@@ -637,7 +627,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         // read allocated, unused memory and are ignored): requested before the barrier, consumed behind it
         float4 dfr[4];
         const float *dfb0 = a.sv.dfs + (tile * TS + pn_row_div(8 * ((tid >> 5) & 7), kinv)) * PN_H + 8 * (tid & 31);
-        if (ew && (K == 8 || K == 4)) {
+        if (K == 8 || K == 4) {
             dfr[0] = *reinterpret_cast<const float4 *>(dfb0); dfr[1] = *reinterpret_cast<const float4 *>(dfb0 + 4);
             if (K == 4) { dfr[2] = *reinterpret_cast<const float4 *>(dfb0 + PN_H); dfr[3] = *reinterpret_cast<const float4 *>(dfb0 + PN_H + 4); }
         }
@@ -645,7 +635,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         rm_cur = rm_nxt; ar_cur = ar_nxt;
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 1);
-        const int rp = bw ? prow[row] : -1;
+        const int rp = prow[row];
         float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0;       // the row's embedding values (for its gradient at the end of the tile)
         if (rp >= 0) {
             const float *ep = a.emb + (long long)rp * PN_F + EPT * q;
@@ -653,8 +643,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         }
         {
             // ---- alpha head backward + dY4 in one pass (b_front): K = 8 / 4 / 2 / 1 with compile-time sample boundaries, any other K at run time
-            if (!ew) { PN_EMU_MATCH_WAVE_SYNC(); }
-            else if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
+            if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
             else if (K == 4) b_front<4, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
             else if (K == 2) b_front<2, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
             else if (K == 1) b_front<1, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
@@ -674,8 +663,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         PN_TR(pn_trace_bwd, 4);
         if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M4, lane, acc);
         else pn_gemm_f16x3_run<16, 8, PN_NFB>(X, W4, lane, acc);
-        pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X, a.sv.dy4k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X + PN_XPLANE, a.sv.dy4m, gtile * 8, tid);
+        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy4k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy4m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 5);
         b_epilogue<MIX>(acc, m3, X, wave, lane);
@@ -688,11 +677,12 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         // ---- layer 3: dY3 -> d h2, and the extras block (input columns 256..262 of W3), K split over the waves
         b_acc_zero(acc);
         PN_TR(pn_trace_bwd, 7);
-        // the extras block first, K split over the first four waves; their partial sums go straight to the tile's free bytes (80 per row and
+        // the extras block first, K split over the four waves; their partial sums go straight to the tile's free bytes (80 per row and
         // plane behind column 255, which no GEMM reads: no barrier needed) -- wave w -> plane w >> 1, 32-byte slot w & 1; a lane holds
-        // features 4 (l >> 5) .. + 3 of rows (l & 31), (l & 31) + 32.  Done before the main GEMM so that its accumulators are dead by then
-        // (an 8-wave workgroup has 128 registers per wave).
-        if (wave < 4) {
+        // features 4 (l >> 5) .. + 3 of rows (l & 31), (l & 31) + 32.  Done before the main GEMM so that its accumulators are dead by then.
+        // (`wave < PN_NW` holds for every wave, but the compiler does not derive it from the launch bound: it emits the test, and without it the
+        //  register allocation of the whole kernel comes out differently from the build that was measured.  Kept, so that the code stays that build's.)
+        if (wave < PN_NW) {
             f32x16 acce[1][2];
             b_acc_zero(acce);
             // (mixed format: wave w takes superchunk w of the block -- the same K split, four f16 chunks and two e4m3 MFMAs per row block)
@@ -705,8 +695,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         }
         if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 9, PN_NFB>(X, M3, lane, acc);
         else pn_gemm_f16x3_run<16, 9, PN_NFB>(X, W3, lane, acc);
-        pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X, a.sv.dy3k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X + PN_XPLANE, a.sv.dy3m, gtile * 8, tid);
+        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy3k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy3m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 8);
         b_epilogue<MIX>(acc, m2, X, wave, lane);
@@ -758,8 +748,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         PN_TR(pn_trace_bwd, 10);
         if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M2, lane, acc);
         else pn_gemm_f16x3_run<16, 8, PN_NFB>(X, W2, lane, acc);
-        pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X, a.sv.dy2k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X + PN_XPLANE, a.sv.dy2m, gtile * 8, tid);
+        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy2k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy2m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 11);
         b_epilogue<MIX>(acc, m1, X, wave, lane);
@@ -772,21 +762,18 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         // one pass of two would hold a third block of accumulators at once)
         [[maybe_unused]] f32x16 acx[1][2];
         [[maybe_unused]] f32x16 (&acc1)[1][2] = *reinterpret_cast<f32x16 (*)[1][2]>(&acc[PN_NFB - 1]);
+        // seven feature blocks over four waves: 2 2 2 1 (XYZG: 2 2 2 3)
         if constexpr (MIX) {
-            if (PN_NFB == 2) {
-                if (wave < 3) pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, PN_NFB>(X, img + PKM_D1, 2 * wave, lane, acc);
-                else {
-                    pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, 6, lane, acc);
-                    if constexpr (XYZG) {
-                        pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 0, lane, acc1);
-                        b_acc_zero(acx);
-                        pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 1, lane, acx);
-                    }
+            if (wave < 3) pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, PN_NFB>(X, img + PKM_D1, 2 * wave, lane, acc);
+            else {
+                pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, 6, lane, acc);
+                if constexpr (XYZG) {
+                    pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 0, lane, acc1);
+                    b_acc_zero(acx);
+                    pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 1, lane, acx);
                 }
-            } else if (wave < PN_MB_D1) {
-                pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, wave, lane, acc);
             }
-        } else if (PN_NFB == 2) {       // seven feature blocks over four waves: 2 2 2 1 (XYZG: 2 2 2 3)
+        } else {
             if (wave < 3) pn_gemm_f16x3<16, PN_MB_D1, PN_NFB>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), 2 * wave, lane, acc);
             else {
                 pn_gemm_f16x3<16, PN_MB_D1, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), 6, lane, acc);
@@ -796,11 +783,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                     pn_gemm_f16x3<16, 2, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1T), 1, lane, acx);
                 }
             }
-        } else if (wave < PN_MB_D1) {      // over eight waves: one each, the last wave idle
-            pn_gemm_f16x3<16, PN_MB_D1, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), wave, lane, acc);
         }
-        pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X, a.sv.dy1k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H, PN_XRS, PN_NW>(X + PN_XPLANE, a.sv.dy1m, gtile * 8, tid);
+        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy1k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy1m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 14);
 #pragma unroll
@@ -813,7 +798,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                         *reinterpret_cast<float4 *>(dx + (32 * rb + (lane & 31)) * LDX + pn_d_feat(PN_NFB * wave + fb, g, lane)) =
                             make_float4(acc[fb][rb][4 * g], acc[fb][rb][4 * g + 1], acc[fb][rb][4 * g + 2], acc[fb][rb][4 * g + 3]);
             }
-        if constexpr (XYZG && PN_NFB == 2) {
+        if constexpr (XYZG) {
             if (wave == 3) {
 #pragma unroll
                 for (int fb = 0; fb < 2; ++fb)
@@ -835,7 +820,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         // read-modify-write: 1 KB of write traffic per row, 7.3 GB per step at the bench configuration).  The values now go back into the
         // row's own d X0 columns (which only their thread reads), and the wave -- it holds 16 whole rows -- sends them out two rows per
         // instruction: lanes 0..31 = the 128-byte gradient row of one point, lanes 32..63 the next row's.
-        if (bw && rp >= 0) {
+        if (rp >= 0) {
             float *dr_ = dx + row * LDX;
             const float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
             float go[EPT];
@@ -857,17 +842,13 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             for (int i = 0; i < EPT; i += 4) *reinterpret_cast<float4 *>(dr_ + EPT * q + i) = make_float4(go[i], go[i + 1], go[i + 2], go[i + 3]);
         }
         PN_WAVE_LDS_SYNC();
-        if (bw) {
-            const int r0w = (row & ~15) + (lane >> 5), col = lane & 31;          // the wave's 16 rows, two per instruction
+        const int r0w = (row & ~15) + (lane >> 5), col = lane & 31;          // the wave's 16 rows, two per instruction
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = r0w + 2 * j, p = prow[r];
-                if (p >= 0) atomicAdd(&a.g_emb[(long long)p * PN_F + col], dx[r * LDX + col]);
-            }
+        for (int j = 0; j < 8; ++j) {
+            const int r = r0w + 2 * j, p = prow[r];
+            if (p >= 0) atomicAdd(&a.g_emb[(long long)p * PN_F + col], dx[r * LDX + col]);
         }
-        if constexpr (XYZG) {
-            if (bw) b_xyz_row(a, dx + row * LDX, gwf, wrow, wnrm, sidx, rp, row, q, K, kinv, invS);
-        }
+        if constexpr (XYZG) b_xyz_row(a, dx + row * LDX, gwf, wrow, wnrm, sidx, rp, row, q, K, kinv, invS);
         PN_TR(pn_trace_bwd, 16);
     }
     // flush the register-resident partial sums: a workgroup that had no tile has nothing to add; the others first add up their eight row
@@ -878,7 +859,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         const int cg = tid0 & 31, rs = tid0 >> 5;
         float *red = reinterpret_cast<float *>(smem_b);            // [8 row sets][256 columns] over the tile's space
         PN_LDS_BARRIER();
-        if (tid0 < PN_ETHR) {                                      // (the front's threads hold the sums)
+        if (tid0 < PN_NTHR) {          // (every thread: see `wave < PN_NW` above)
 #pragma unroll
             for (int c = 0; c < 8; ++c) red[rs * PN_H + 8 * cg + c] = gw5[c];
             if (cg == 0) red[8 * PN_H + rs] = gb5t;
@@ -1099,23 +1080,44 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_f16(const float *__restric
     }
 }
 
-template <int NFB, int MF, int RS, int NST, bool TWO = false>
-int launch_wgrad_f16(const uint4 *A, const uint4 *B, const int *d_tiles, long long rows_max, float *partial, const unsigned *gscale,
-                     float *grad, int dst_w, int ldc, int Nreal, int bias_col, int dst_b, hipStream_t s, const uint4 *Am = nullptr, const uint4 *Bm = nullptr) {
+// one layer's weight-gradient GEMM: dW[dst_w .. : ldc] (the first `nreal` columns) and, from column `bias_col` (or -1), db[dst_b ..]
+enum WgShape { WG_288x256, WG_256x256, WG_288x128, WG_128x128 };      // X columns x dY columns: <NFB, MF> of k_wgrad_f16
+struct WgLayer {
+    WgShape shape;
+    const uint4 *dy, *x, *dym, *xm;     // the k-major operands and (two-plane mode; null otherwise) their residual planes
+    const int *d_tiles;                 // the device's count of 64-row tiles to walk
+    long long rows_max;                 // its host bound: the allocation
+    int dst_w, ldc, nreal, bias_col, dst_b;
+};
+template <int NFB, int MF, int RS, int NST, bool TWO>
+int launch_wgrad_f16(const WgLayer &L, float *partial, const unsigned *gscale, float *grad, hipStream_t s) {
     int chunks = WG_CHUNKS;
-    const long long tiles = rows_max / PN_TILE;
+    const long long tiles = L.rows_max / PN_TILE;
     if (tiles < chunks) chunks = (int)(tiles > 0 ? tiles : 1);
     if ((size_t)chunks * 256 * 288 > PARTIAL_FLOATS) return PNERF_E_WS;
-    if (TWO && (!Am || !Bm)) return PNERF_E_INVAL;
+    if (TWO && (!L.dym || !L.xm)) return PNERF_E_INVAL;
     constexpr size_t lds = ((size_t)NST * (TWO ? 2 : 1) * (RS / 8) * (MF + NFB) + 64) * 16;   // the stages [dY | X] (TWO: both planes of each) + the pad slot
     static_assert(lds <= 160 * 1024, "wgrad ring");
     if (hipFuncSetAttribute((const void *)k_wgrad_f16<NFB, MF, RS, NST, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return PNERF_E_LAUNCH;
     { PnProfScope prof(PNK_WGRAD, s);
-    hipLaunchKernelGGL((k_wgrad_f16<NFB, MF, RS, NST, TWO>), dim3(chunks), dim3(512), lds, s, A, B, d_tiles, partial, Am, Bm); }
+    hipLaunchKernelGGL((k_wgrad_f16<NFB, MF, RS, NST, TWO>), dim3(chunks), dim3(512), lds, s, L.dy, L.x, L.d_tiles, partial, L.dym, L.xm); }
     PnProfScope prof(PNK_WGRAD_REDUCE, s);
-    hipLaunchKernelGGL(k_wgrad_reduce_f16, dim3(pn_cdiv((long long)MF * 288, 64)), dim3(256), 0, s, partial, chunks, MF, Nreal, bias_col, gscale, grad, dst_w, ldc, dst_b);
+    hipLaunchKernelGGL(k_wgrad_reduce_f16, dim3(pn_cdiv((long long)MF * 288, 64)), dim3(256), 0, s, partial, chunks, MF, L.nreal, L.bias_col, gscale, grad, L.dst_w, L.ldc, L.dst_b);
     PN_CHECK_LAUNCH();
     return 0;
+}
+// the instance for a layer's shape.  One plane: PN_WG_RS-row stages for the aggregator layers, 16-row stages x 4 for the colour layers.  Two planes:
+// dW = dYh^T Xh + dYh^T Xm + dYm^T Xh in ONE pass per layer (a stage holds both planes of both operands; round 4 ran the one-plane kernel three
+// times per layer), 16-row stages everywhere: four planes of 32 rows would not leave four ring slots.
+template <bool TWO>
+int launch_wgrad_layer(const WgLayer &L, float *partial, const unsigned *gscale, float *grad, hipStream_t s) {
+    constexpr int RS = TWO ? 16 : PN_WG_RS, NST = TWO ? 4 : PN_WG_NST;
+    switch (L.shape) {
+        case WG_288x256: return launch_wgrad_f16<PN_NF1, PN_H, RS, NST, TWO>(L, partial, gscale, grad, s);
+        case WG_256x256: return launch_wgrad_f16<PN_H, PN_H, RS, NST, TWO>(L, partial, gscale, grad, s);
+        case WG_288x128: return launch_wgrad_f16<PN_NF1, PN_HC, 16, 4, TWO>(L, partial, gscale, grad, s);
+        default: return launch_wgrad_f16<PN_HC, PN_HC, 16, 4, TWO>(L, partial, gscale, grad, s);
+    }
 }
 
 
@@ -1398,11 +1400,11 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     a.conf = pts->conf; a.zo_gs = x0_saved ? nullptr : pg->zero_one_gscale; a.zo_eps = pg->zero_one_eps;       // (the fused render path only)
     if (a.zo_gs && !a.conf) return PNERF_E_INVAL;
     if (!a.g_emb || !a.g_conf || !a.g_dir || !a.g_color) return PNERF_E_INVAL;
-    // xyz_grad: the fused render path (world-coordinate distances recomputed from xyz / sample_loc), 4-wave organisation
+    // xyz_grad: the fused render path (world-coordinate distances recomputed from xyz / sample_loc)
     BwdXArgs ax;
     ax.xyz = pts->xyz; ax.sample_loc = d_sample_loc; ax.g_xyz = pg->xyz;
     const bool xg = ax.g_xyz != nullptr;
-    if (xg && (x0_saved || PN_NFB != 2)) return PNERF_E_UNSUP;
+    if (xg && x0_saved) return PNERF_E_UNSUP;
     if (xg && (!ax.xyz || !ax.sample_loc)) return PNERF_E_INVAL;
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) != hipSuccess) return PNERF_E_LAUNCH;
@@ -1412,12 +1414,14 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     const size_t lds_c = CB_BYTES, lds_a = xg ? BL_BYTES_X : BL_BYTES;
     const bool wg2 = sv.wg2 != 0;                      // two-plane weight-gradient mode (the forward of this step ran in it: same process-wide setting)
     if (wg2) x0_saved = true;
-    const void *kcb = wg2 ? (const void *)k_color_backward<true> : (const void *)k_color_backward<false>;
     const bool mix = !wg2 && (pn_mix_mask() & 4);      // mixq.h: e4m3 cross terms in the input-gradient chain
-    const void *kab = xg ? (wg2 ? (const void *)k_agg_backward<true, false, true> : mix ? (const void *)k_agg_backward<false, true, true> : (const void *)k_agg_backward<false, false, true>)
-                         : (wg2 ? (const void *)k_agg_backward<true> : mix ? (const void *)k_agg_backward<false, true> : (const void *)k_agg_backward<false>);
-    if (hipFuncSetAttribute(kcb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipFuncSetAttribute(kab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
+    // the one place that names the kernel instances: these selections serve both the LDS attribute and the launch (the tile kernel's argument
+    // struct follows from xg: the pointer types keep kernel and struct paired)
+    void (*const kcb)(BwdArgs) = wg2 ? k_color_backward<true> : k_color_backward<false>;
+    void (*const kab)(BwdArgs) = wg2 ? k_agg_backward<true> : mix ? k_agg_backward<false, true> : k_agg_backward<false>;
+    void (*const kax)(BwdXArgs) = wg2 ? k_agg_backward<true, false, true> : mix ? k_agg_backward<false, true, true> : k_agg_backward<false, false, true>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kcb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipFuncSetAttribute(xg ? reinterpret_cast<const void *>(kax) : reinterpret_cast<const void *>(kab), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
     // the forward left the class partition of the valid samples in the saved area (aggregate.hip: pn_classify)
     a.cls_list = sv.cls_list; a.cls_info = sv.cls_info; a.valid_list = sv.cls_list;
     // the scale of this call's gradients (a power of two derived on the device from max |d decoded| over the valid samples)
@@ -1428,8 +1432,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     }
     if (a.zo_gs) hipLaunchKernelGGL(k_zero_one_empty, dim3(1), dim3(1), 0, s, a.conf, d_counters, (long long)SR * K, a.zo_gs, a.zo_eps, a.g_conf);
     { PnProfScope prof(PNK_COLOR_BWD, s);
-      if (wg2) hipLaunchKernelGGL(k_color_backward<true>, dim3(grid_c), dim3(256), lds_c, s, a);
-      else hipLaunchKernelGGL(k_color_backward<false>, dim3(grid_c), dim3(256), lds_c, s, a); }
+      hipLaunchKernelGGL(kcb, dim3(grid_c), dim3(256), lds_c, s, a); }
     int kc[PN_NCLS];
     const int ncls = pn_class_slots(K, kc);
     { PnProfScope prof(PNK_AGG_BWD, s);
@@ -1437,13 +1440,8 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
           a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
           const long long tiles = (n_valid + a.TS - 1) / a.TS;                    // worst-case grid, two workgroups per CU
           const int grid_a = (int)(tiles < 2LL * ncu ? (tiles > 0 ? tiles : 1) : 2LL * ncu);
-          if (xg) static_cast<BwdArgs &>(ax) = a;
-          if (xg && wg2) hipLaunchKernelGGL((k_agg_backward<true, false, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax);
-          else if (xg && mix) hipLaunchKernelGGL((k_agg_backward<false, true, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax);
-          else if (xg) hipLaunchKernelGGL((k_agg_backward<false, false, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax);
-          else if (wg2) hipLaunchKernelGGL(k_agg_backward<true>, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-          else if (mix) hipLaunchKernelGGL((k_agg_backward<false, true>), dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
-          else hipLaunchKernelGGL(k_agg_backward<false>, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
+          if (xg) { static_cast<BwdArgs &>(ax) = a; hipLaunchKernelGGL(kax, dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax); }
+          else hipLaunchKernelGGL(kab, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
       } }
     PN_CHECK_LAUNCH();
     // the point gradients are final here: let a data-parallel caller start their all-reduce behind this event while the
@@ -1452,43 +1450,32 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     // weight gradients over every tile of every class (+ their zero padding tiles): the tile count lives on the device, the host
     // bound is the allocation.  samples: only the first n_valid rows of fs / pe / c1.. exist -- the GEMM masks the rest of the
     // last colour tile (0 * stale bits could be NaN)
-    const long long rows = sv.rows, smp = n_valid;
-    const int *dt = sv.cls_info + PN_CI_TILES;
-    int rc;
-    float *g = d_grad_params;
-    const int *ct = sv.cls_info + PN_CI_CTILES;
-    if (wg2) {
-        // two-plane weight-gradient mode: dW = dYh^T Xh + dYh^T Xm + dYm^T Xh in ONE pass per layer (k_wgrad_f16<.., TWO>: a stage holds both planes of
-        // both operands; round 4 ran the one-plane kernel three times per layer).  16-row stages: four planes of 32 rows would not leave four ring slots.
-        // The bias gradients take both planes of dY: the operands' own ones column (layers 1 and 3) has a zero residual, the constant-ones tail
-        // (layers 2 and 4) is multiplied with dYh and dYm.
-        if ((rc = launch_wgrad_f16<PN_NF1, PN_H, 16, 4, true>(sv.dy1k, sv.x0k, dt, rows, d_partials, sv.gscale, g, PO_W1, PN_IN1, PN_IN1, PN_ONES1, PO_B1, s, sv.dy1m, sv.x0m))) return rc;
-        if ((rc = launch_wgrad_f16<PN_H, PN_H, 16, 4, true>(sv.dy2k, sv.h1k, dt, rows, d_partials, sv.gscale, g, PO_W2, PN_H, PN_H, PN_H, PO_B2, s, sv.dy2m, sv.h1m))) return rc;
-        if ((rc = launch_wgrad_f16<PN_NF1, PN_H, 16, 4, true>(sv.dy3k, sv.h2k, dt, rows, d_partials, sv.gscale, g, PO_W3, PN_IN3, PN_IN3, PN_ONES3, PO_B3, s, sv.dy3m, sv.h2m))) return rc;
-        if ((rc = launch_wgrad_f16<PN_H, PN_H, 16, 4, true>(sv.dy4k, sv.h3k, dt, rows, d_partials, sv.gscale, g, PO_W4, PN_H, PN_H, PN_H, PO_B4, s, sv.dy4m, sv.h3m))) return rc;
-        // the three colour layers: samples instead of neighbor rows, 128 output features; their bias gradients were summed by k_color_backward
-        if ((rc = launch_wgrad_f16<PN_NF1, PN_HC, 16, 4, true>(sv.dc1k, sv.xck, ct, sv.samples, d_partials, sv.gscale, g, PO_WC1, PN_INC, PN_INC, -1, 0, s, sv.dc1m, sv.xcm))) return rc;
-        if ((rc = launch_wgrad_f16<PN_HC, PN_HC, 16, 4, true>(sv.dc2k, sv.c1k, ct, sv.samples, d_partials, sv.gscale, g, PO_WC2, PN_HC, PN_HC, -1, 0, s, sv.dc2m, sv.c1m))) return rc;
-        if ((rc = launch_wgrad_f16<PN_HC, PN_HC, 16, 4, true>(sv.dc3k, sv.c2k, ct, sv.samples, d_partials, sv.gscale, g, PO_WC3, PN_HC, PN_HC, -1, 0, s, sv.dc3m, sv.c2m))) return rc;
-        (void)smp;
-        return 0;
+    (void)R;
+    const long long rows = sv.rows, smps = sv.samples;
+    const int *dt = sv.cls_info + PN_CI_TILES, *ct = sv.cls_info + PN_CI_CTILES;
+    // the four aggregator layers (the bias gradients are the operands' own ones column in layers 1 and 3, the constant-ones tail in layers 2 and
+    // 4; in two-plane mode they take both planes of dY: the ones column has a zero residual, the tail is multiplied with dYh and dYm), then the
+    // three colour layers: samples instead of neighbor rows, 128 output features; their bias gradients were summed by k_color_backward
+    const WgLayer layers[7] = {
+        {WG_288x256, sv.dy1k, sv.x0k, sv.dy1m, sv.x0m, dt, rows, PO_W1, PN_IN1, PN_IN1, PN_ONES1, PO_B1},
+        {WG_256x256, sv.dy2k, sv.h1k, sv.dy2m, sv.h1m, dt, rows, PO_W2, PN_H, PN_H, PN_H, PO_B2},
+        {WG_288x256, sv.dy3k, sv.h2k, sv.dy3m, sv.h2m, dt, rows, PO_W3, PN_IN3, PN_IN3, PN_ONES3, PO_B3},
+        {WG_256x256, sv.dy4k, sv.h3k, sv.dy4m, sv.h3m, dt, rows, PO_W4, PN_H, PN_H, PN_H, PO_B4},
+        {WG_288x128, sv.dc1k, sv.xck, sv.dc1m, sv.xcm, ct, smps, PO_WC1, PN_INC, PN_INC, -1, 0},
+        {WG_128x128, sv.dc2k, sv.c1k, sv.dc2m, sv.c1m, ct, smps, PO_WC2, PN_HC, PN_HC, -1, 0},
+        {WG_128x128, sv.dc3k, sv.c2k, sv.dc3m, sv.c2m, ct, smps, PO_WC3, PN_HC, PN_HC, -1, 0},
+    };
+    for (const WgLayer &L : layers) {
+        int rc;
+        if (&L == layers && !x0_saved) {       // layer 1 on the fused path: X0 rebuilt from the gather (the stand-alone aggregator's forward saved its planes)
+            WgX0Args wa;
+            wa.rmeta = sv.rmeta; wa.emb = pts->embedding; wa.x0t = sv.x0k; wa.n_points = pts->n;
+            rc = launch_wgrad_x0(L.dy, wa, dt, rows, d_partials, sv.gscale, d_grad_params, s);
+        } else {
+            rc = wg2 ? launch_wgrad_layer<true>(L, d_partials, sv.gscale, d_grad_params, s) : launch_wgrad_layer<false>(L, d_partials, sv.gscale, d_grad_params, s);
+        }
+        if (rc) return rc;
     }
-    if (x0_saved) {        // the stand-alone aggregator (perspective coordinates from its caller): X0 planes saved by the forward
-        if ((rc = launch_wgrad_f16<PN_NF1, PN_H, PN_WG_RS, PN_WG_NST>(sv.dy1k, sv.x0k, dt, rows, d_partials, sv.gscale, g, PO_W1, PN_IN1, PN_IN1, PN_ONES1, PO_B1, s))) return rc;
-    } else {               // the fused path: X0 rebuilt from the gather
-        (void)d_sample_loc; (void)R;
-        WgX0Args wa;
-        wa.rmeta = sv.rmeta; wa.emb = pts->embedding; wa.x0t = sv.x0k; wa.n_points = pts->n;
-        if ((rc = launch_wgrad_x0(sv.dy1k, wa, dt, rows, d_partials, sv.gscale, g, s))) return rc;
-    }
-    if ((rc = launch_wgrad_f16<PN_H, PN_H, PN_WG_RS, PN_WG_NST>(sv.dy2k, sv.h1k, dt, rows, d_partials, sv.gscale, g, PO_W2, PN_H, PN_H, PN_H, PO_B2, s))) return rc;
-    if ((rc = launch_wgrad_f16<PN_NF1, PN_H, PN_WG_RS, PN_WG_NST>(sv.dy3k, sv.h2k, dt, rows, d_partials, sv.gscale, g, PO_W3, PN_IN3, PN_IN3, PN_ONES3, PO_B3, s))) return rc;
-    if ((rc = launch_wgrad_f16<PN_H, PN_H, PN_WG_RS, PN_WG_NST>(sv.dy4k, sv.h3k, dt, rows, d_partials, sv.gscale, g, PO_W4, PN_H, PN_H, PN_H, PO_B4, s))) return rc;
-    // the three colour layers: samples instead of neighbor rows, 128 output features; their bias gradients were summed by k_color_backward
-    (void)smp;
-    if ((rc = launch_wgrad_f16<PN_NF1, PN_HC, 16, 4>(sv.dc1k, sv.xck, ct, sv.samples, d_partials, sv.gscale, g, PO_WC1, PN_INC, PN_INC, -1, 0, s))) return rc;
-    if ((rc = launch_wgrad_f16<PN_HC, PN_HC, 16, 4>(sv.dc2k, sv.c1k, ct, sv.samples, d_partials, sv.gscale, g, PO_WC2, PN_HC, PN_HC, -1, 0, s))) return rc;
-    if ((rc = launch_wgrad_f16<PN_HC, PN_HC, 16, 4>(sv.dc3k, sv.c2k, ct, sv.samples, d_partials, sv.gscale, g, PO_WC3, PN_HC, PN_HC, -1, 0, s))) return rc;
     return 0;
 }
 

@@ -55,33 +55,17 @@ enum : int {
 
 // Streaming stores of the saved planes (whole 1 KB runs per wave-instruction, written once, read by another kernel much later):
 // non-temporal stores.  Round 3 compared the cache-policy bits on one box, whole step: plain 42.1 ms, nt 41.3 (shipped), sc1 (write-through,
-// line dropped from L2) 41.8, nt sc1 41.0 -- inside the box-to-box noise, so the builtin stays (the sc bits have no builtin; the dev variants
-// below go through inline asm, which needs its own s_nop against the store-data hazard: without it the data registers are overwritten
-// while the 16-byte store still reads them -- the NaN-poisoned parity tests caught exactly that).
-// dev A/B (tools/_build only): -DPN_STREAM_STORE_ASM='"nt sc1"' etc., -DPN_PLAIN_STREAM_STORES, -DPN_NO_STREAM_STORES (drops the stores:
-// results are garbage, the timing tells what they cost: forward -21 %, backward -10 %).
-#if defined(PN_NO_STREAM_STORES)
-#define PN_STREAM_STORE(val, ptr) ((void)(val), (void)(ptr))
-#elif defined(PN_PLAIN_STREAM_STORES) || defined(PN_EMU)
+// line dropped from L2) 41.8, nt sc1 41.0 -- inside the box-to-box noise, so the builtin stays.  (Dropping the stores altogether: forward
+// -21 %, backward -10 %: that is what they cost.)
+#ifdef PN_EMU
 #define PN_STREAM_STORE(val, ptr) (*(ptr) = (val))
-#elif defined(PN_STREAM_STORE_ASM)
-__device__ __forceinline__ void pn_stream_store_asm(pn_f4 v, pn_f4 *p) {
-    // (s_nop 1: a 16-byte store reads its data registers over several cycles; the compiler pads its own stores against a following write of
-    //  those registers, but it does not know that this asm is one)
-    asm volatile("global_store_dwordx4 %0, %1, off " PN_STREAM_STORE_ASM "\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-}
-#define PN_STREAM_STORE(val, ptr) pn_stream_store_asm((val), (ptr))
 #else
 #define PN_STREAM_STORE(val, ptr) __builtin_nontemporal_store((val), (ptr))
 #endif
 
 // stores of fp32 rows straight from the accumulator layout (a lane pair writes 32 bytes, the wave's four stores of a row fill one
-// 128-byte line): plain stores, so that L2 merges them into whole lines (dev A/B: -DPN_REG_STORE_NT)
-#ifdef PN_REG_STORE_NT
-#define PN_REG_STORE(val, ptr) __builtin_nontemporal_store((val), (ptr))
-#else
+// 128-byte line): plain stores, so that L2 merges them into whole lines
 #define PN_REG_STORE(val, ptr) (*(ptr) = (val))
-#endif
 
 // Workgroup barrier for LDS hazards only.  __syncthreads() carries a full fence: hipcc emits s_waitcnt vmcnt(0) in front of the
 // s_barrier, i.e. every barrier would also wait for the fire-and-forget stores of the copy-outs (HBM round trips) and for the next
@@ -97,13 +81,12 @@ __device__ __forceinline__ void pn_stream_store_asm(pn_f4 v, pn_f4 *p) {
 // the angle error is <= 2 x 2 pi 2^-25 = 3.7e-7 rad for EVERY octave and every |x| < 2^20 (learned embeddings reach several units) -- and
 // then evaluated by v_sin_f32 / v_cos_f32 (input in revolutions).  Round 2 took one __sinf / __cosf of x (a single-term x / 2pi, error
 // growing with |x|) and doubled the angle by recurrence (error doubling per octave); same instruction count within 30 %.
-// -DPN_EXACT_SINCOS: libm's sincosf per octave (dev A/B only).
 template <int NF>
 __device__ __forceinline__ void pn_pe_octaves(float x, float (&s)[NF], float (&c)[NF]) {
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
         const float xf = x * (float)(1 << f);
-#if defined(PN_EXACT_SINCOS) || defined(PN_EMU)
+#ifdef PN_EMU
         sincosf(xf, &s[f], &c[f]);
 #else
         const float k = __builtin_rintf(xf * 0.15915494f);
@@ -232,19 +215,6 @@ __device__ __forceinline__ void pn_x_axpy4(const char *X, int row, int col, floa
 #ifndef PN_WPF
 #define PN_WPF 2
 #endif
-// dev experiments (tools/_build variants only): issue-slot spacing after every MFMA / wave priority during the GEMM
-#if defined(PN_MFMA_NOPS) && !defined(PN_EMU)
-#define PN_MFMA_GAP() do { asm volatile("s_nop %0\n\ts_nop %0" ::"n"(PN_MFMA_NOPS)); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define PN_MFMA_GAP() ((void)0)
-#endif
-#if defined(PN_GEMM_PRIO) && !defined(PN_EMU)
-#define PN_GEMM_PRIO_BEGIN() __builtin_amdgcn_s_setprio(PN_GEMM_PRIO)
-#define PN_GEMM_PRIO_END() __builtin_amdgcn_s_setprio(0)
-#else
-#define PN_GEMM_PRIO_BEGIN() ((void)0)
-#define PN_GEMM_PRIO_END() ((void)0)
-#endif
 // (Measured, round 2: with every chunk reading chunk 0's fragments -- the weight stream then hits L1 -- the forward is 11 % and the
 //  backward 15 % faster: that is what the L2 -> L1 weight traffic (1.07 MB per 64-row tile and workgroup) costs, and the bound on what
 //  a larger register blocking could recover.  A prefetch distance of 3 chunks instead of 2, starting the CU's second workgroup half
@@ -314,7 +284,6 @@ __device__ __forceinline__ void pn_gemm_f16x3_run(const char *X, PnGemmW<NC, MB,
         }
     };
     load_x(std::integral_constant<int, 0>{});
-    PN_GEMM_PRIO_BEGIN();
     pn_static_for<NC>([&](auto cc) {
         constexpr int c = decltype(cc)::value, sw = c % NS, sx = c & 1;
         if constexpr (c + PF < NC) W.template load<c + PF>();
@@ -331,11 +300,9 @@ __device__ __forceinline__ void pn_gemm_f16x3_run(const char *X, PnGemmW<NC, MB,
                     const pn_h8 a = __builtin_bit_cast(pn_h8, p == 2 ? W.wm[sw][fb] : W.wh[sw][fb]);
                     const pn_h8 b = __builtin_bit_cast(pn_h8, p == 1 ? xm[sx][rb] : xh[sx][rb]);
                     acc[fb][rb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[fb][rb], 0, 0, 0);
-                    PN_MFMA_GAP();
                 }
         __builtin_amdgcn_sched_barrier(0);
     });
-    PN_GEMM_PRIO_END();
 }
 
 template <int NC, int MB, int NFB, int WPF = PN_WPF, int NP = 3, int XRS = PN_XRS, int XPL = PN_XPLANE, int AF>
@@ -360,14 +327,14 @@ __device__ __forceinline__ uint2 pn_lds_read_tr16(const char *p) {
     return __builtin_bit_cast(uint2, r);
 }
 // the high plane only ([rg_total][NF] units): the dY operand of the weight-gradient GEMM
-// NW = waves of the calling workgroup: wave w copies the row groups 8 / NW * w .. (8 of them in a 64-row tile)
-template <int NF, int XRS = PN_XRS, int NW = 4>
+// wave w of the workgroup's four copies the row groups 2 w, 2 w + 1 (8 of them in a 64-row tile)
+template <int NF, int XRS = PN_XRS>
 __device__ __forceinline__ void pn_copy_out_kmajor_h(const char *X, uint4 *__restrict__ dst, long long rg0, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     const int blk = ((lane >> 2) & 3) * XRS + ((lane >> 4) * 16 + (lane & 3) * 4) * 2;
 #pragma unroll
-    for (int i = 0; i < 8 / NW; ++i) {
-        const int rg = wave * (8 / NW) + i;
+    for (int i = 0; i < 2; ++i) {
+        const int rg = wave * 2 + i;
         const char *src = X + rg * 8 * XRS + blk;
         uint4 *d = dst + (rg0 + rg) * NF;
         // (all transposing reads of the run first, then its stores: the stores are inline asm, which the scheduler does not move loads across)
@@ -397,14 +364,14 @@ __device__ __forceinline__ uint2 pn_rne_rest(uint2 h, uint2 m, uint2 s) {
     return __builtin_bit_cast(uint2, mm - (ss - hh));
 }
 // TWO: also write the residual plane to dstm (same layout) -- the fp32-class weight-gradient mode
-template <int NF, bool TWO = false, int NW = 4>
+template <int NF, bool TWO = false>
 __device__ __forceinline__ void pn_copy_out_kmajor(const char *X, uint4 *__restrict__ dst, long long rg0, int tid, uint4 *__restrict__ dstm = nullptr) {
     const int lane = tid & 63, wave = tid >> 6;
     const int blk = ((lane >> 2) & 3) * PN_XRS + ((lane >> 4) * 16 + (lane & 3) * 4) * 2;      // this lane's slot inside a [4][64-column] block
     constexpr int NJ = (NF + 63) / 64;
 #pragma unroll
-    for (int i = 0; i < 8 / NW; ++i) {
-        const int rg = wave * (8 / NW) + i;
+    for (int i = 0; i < 2; ++i) {
+        const int rg = wave * 2 + i;
         const char *src = X + rg * 8 * PN_XRS + blk;
         uint4 *d = dst + (rg0 + rg) * NF;
         uint2 lo[NJ], hi[NJ], lom[NJ], him[NJ];
@@ -432,14 +399,14 @@ __device__ __forceinline__ void pn_copy_out_kmajor(const char *X, uint4 *__restr
 
 // the tile's columns C0 .. C0 + 63 -> one k-major plane of 64 features ([rg_total][64] units): the saved part of X0 on the fused path
 // (the weight-gradient kernel rebuilds the rest from the embedding: backward.hip k_wgrad_x0)
-template <int C0, int NW = 4>
+template <int C0>
 __device__ __forceinline__ void pn_copy_out_kmajor_cols64(const char *X, uint4 *__restrict__ dst, long long rg0, int tid) {
     static_assert(C0 % 16 == 0, "a 16-column group boundary");
     const int lane = tid & 63, wave = tid >> 6;
     const int blk = ((lane >> 2) & 3) * PN_XRS + ((lane >> 4) * 16 + (lane & 3) * 4) * 2 + C0 * 2;
 #pragma unroll
-    for (int i = 0; i < 8 / NW; ++i) {
-        const int rg = wave * (8 / NW) + i;
+    for (int i = 0; i < 2; ++i) {
+        const int rg = wave * 2 + i;
         const char *src = X + rg * 8 * PN_XRS + blk;
         const uint2 lo = pn_lds_read_tr16(src), hi = pn_lds_read_tr16(src + 4 * PN_XRS);
         const uint2 lom = pn_lds_read_tr16(src + PN_XPLANE), him = pn_lds_read_tr16(src + PN_XPLANE + 4 * PN_XRS);

@@ -150,6 +150,7 @@ __device__ __forceinline__ void pn_xt_store4(char *X, int row, int col, float v0
 // NSR = superchunks this GEMM runs (4, or 1: the layer-3 extras block of the backward, one superchunk per wave).
 template <int NSR, int NT, int MB, int NFB, int LEAD = PN_MIX_LEAD>
 struct PnMixW {
+    static_assert(LEAD <= 2, "wsc[fb] is one register: with LEAD >= 3 it is reloaded before the previous superchunk's MFMAs have read it");
     static constexpr int NU = 4 * NSR + NT, PF = LEAD < NU ? LEAD : NU, NS = LEAD + 1;
     uint4 r[NS][NFB][2];
     unsigned wsc[NFB];
@@ -241,7 +242,6 @@ __device__ __forceinline__ void pn_gemm_mix_run(const char *X, PnMixW<NSR, NT, M
         }
     };
     load_x(std::integral_constant<int, 0>{});
-    PN_GEMM_PRIO_BEGIN();
     pn_static_for<NU>([&](auto uu) {
         constexpr int u = decltype(uu)::value, sw = u % NS, sx = u & 1;
         if constexpr (u + LEAD < NU) W.template load<u + LEAD>();
@@ -279,7 +279,6 @@ __device__ __forceinline__ void pn_gemm_mix_run(const char *X, PnMixW<NSR, NT, M
         }
         __builtin_amdgcn_sched_barrier(0);
     });
-    PN_GEMM_PRIO_END();
 }
 
 template <int NSR, int NT, int MB, int NFB, int LEAD = PN_MIX_LEAD, int AF>
@@ -291,14 +290,14 @@ __device__ __forceinline__ void pn_gemm_mix(const char *X, const char *img, int 
 
 // the tile's columns C0 .. C0 + 63 of the HIGH plane -> one k-major plane of 64 features (pn_copy_out_kmajor_cols64 without the residual: the mixed
 // tile's h is already the nearest f16)
-template <int C0, int NW = 4>
+template <int C0>
 __device__ __forceinline__ void pn_copy_out_kmajor_cols64_h(const char *X, uint4 *__restrict__ dst, long long rg0, int tid) {
     static_assert(C0 % 16 == 0, "a 16-column group boundary");
     const int lane = tid & 63, wave = tid >> 6;
     const int blk = ((lane >> 2) & 3) * PN_XRS + ((lane >> 4) * 16 + (lane & 3) * 4) * 2 + C0 * 2;
 #pragma unroll
-    for (int i = 0; i < 8 / NW; ++i) {
-        const int rg = wave * (8 / NW) + i;
+    for (int i = 0; i < 2; ++i) {
+        const int rg = wave * 2 + i;
         const char *src = X + rg * 8 * PN_XRS + blk;
         const uint2 lo = pn_lds_read_tr16(src), hi = pn_lds_read_tr16(src + 4 * PN_XRS);
         pn_f4 t = {__uint_as_float(lo.x), __uint_as_float(lo.y), __uint_as_float(hi.x), __uint_as_float(hi.y)};

@@ -15,22 +15,15 @@
 #define PN_HC     128
 #define PN_TILE   64                 // neighbor rows per aggregator tile (2 MFMA row tiles).  Measured: 32-row tiles are 10 % slower (twice the weight-fragment traffic per MFMA)
 #define PN_MT     (PN_TILE / 32)
-// Organisation of an aggregator workgroup (forward and backward tile kernels), two workgroups per CU either way:
-//   PN_NTHR 256 ("A", shipped): 4 waves x (2 feature blocks x 2 row blocks of the 64-row tile), up to 256 registers per wave, two waves per SIMD
-//   PN_NTHR 512 ("B", dev: EXTRA_DEFS=-DPN_NTHR=512): 8 waves, each ONE feature block x both row blocks in the GEMM phases (32 accumulator
-//                registers, 128 registers per wave, four waves per SIMD); the row-wise phases keep A's 4-threads-per-row mapping, split by role:
-//                waves 4..7 gather / build / embedding gradient, waves 0..3 tail / front.  Round 4 built and measured it on request of the
-//                round-3 review (tools/gemm_probe.hip had it 7 % ahead on a synthetic chain): parity green, but the REAL kernels are slower,
-//                forward 12.78 -> 14.56 ms, backward 13.85 -> 14.82 ms, render-only 5.18 -> 4.68 M rays/s -- every wave reads BOTH row blocks of
-//                the tile from LDS for half as many MFMAs, the LDS pipe is busy 33 % longer and the waves wait 3.7 x as long for an LDS issue
-//                slot (SQ_WAIT_INST_LDS), MFMA busy 0.49 -> 0.42 (profiles/r04_orgB_vs_orgA.txt).  One source for both.
-#ifndef PN_NTHR
-#define PN_NTHR   256
-#endif
-#define PN_NW     (PN_NTHR / 64)     // waves per aggregator workgroup
-#define PN_NFB    (8 / PN_NW)        // 32-feature blocks per wave in the 256-wide GEMMs
-#define PN_ETHR   256                // threads of the row-wise element-wise phases
-#define PN_TPR    (PN_ETHR / PN_TILE)     // threads per tile row in those phases
+// Organisation of an aggregator workgroup (forward and backward tile kernels): 4 waves, each 2 feature blocks x 2 row blocks of the 64-row tile,
+// two workgroups per CU, 4 threads per tile row in the row-wise phases.  It is the only one: an 8-wave organisation (one feature block per wave,
+// roles split between waves 0..3 and 4..7) was built in round 4 and measured slower in the real kernels, forward 12.78 -> 14.56 ms, backward
+// 13.85 -> 14.82 ms (profiles/r04_orgB_vs_orgA.txt); its source was last present in commit 0554797.
+#define PN_NTHR   256                // threads of an aggregator workgroup
+#define PN_NW     4                  // its waves
+#define PN_NFB    2                  // 32-feature blocks per wave in the 256-wide GEMMs
+static_assert(PN_NTHR == 64 * PN_NW && PN_NW == 4 && PN_NW * PN_NFB == 8, "the tile kernels are written for 4 waves x 2 of the 8 feature blocks each");
+#define PN_TPR    (PN_NTHR / PN_TILE)     // threads per tile row in the row-wise phases
 #define PN_CTILE  64                 // valid samples per colour-MLP tile
 
 // flat parameter vector (state_dict order, torch [out,in] row-major)
