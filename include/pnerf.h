@@ -347,6 +347,22 @@ int pnerf_extract_2d(const float *d_cam_xyz, int64_t n_points, const pnerf_view_
 int pnerf_point_dirs(const float *d_cam_xyz, int64_t n_points, const float *cam_pos_cam_host, int n_views, const float *rot1_host9,
                      const float *rot2_host9, float *d_dirs, void *stream);
 
+/* ---- evaluation scores of a rendered image against its ground truth (run/evaluate.py:55-61,76 report_metrics: compare_psnr,
+ * compare_ssim(gt, img, 11, multichannel=True) and mean_squared_error over the PNGs that utils/visualizer.py:58-59 wrote).
+ * d_img / d_gt [H,W,3] f32.  quantize8 != 0 first maps every pixel of both images through that PNG round trip,
+ * q = (float)(uint8)(clip(x, 0, 1) * 255.f) / 255.f (the conversion truncates; the division is fp32).  d_out4 (4 doubles):
+ *   [0]     sum of squared differences over all H*W*3 elements      (mse = [0] / (H*W*3); psnr = 10 log10(1 / mse); rmse = sqrt(mse))
+ *   [1..3]  per channel, the sum over the (H-win+1) x (W-win+1) windows fully inside the image of skimage's SSIM map in its uniform-filter
+ *           form (window means, covariance scaled by NP/(NP-1), C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2); skimage's reflected
+ *           border is cropped before its mean, so  ssim = ([1] + [2] + [3]) / (3 (H-win+1)(W-win+1)).  The reference's call passes float
+ *           images and no data_range to skimage <= 0.18, which makes data_range = 2 (while its PSNR takes 1).
+ * All arithmetic is fp64 on the fp32 pixels; no atomics: two calls on the same inputs give the same bits.  PNERF_E_INVAL: null pointer,
+ * win even or < 3, H < win or W < win (skimage raises there), data_range <= 0; PNERF_E_WS: workspace too small; PNERF_E_UNSUP: win > 25
+ * (the tile and its halo no longer fit the LDS) or an image of more than 65 535 x 16 window rows / 2^31 - 1 tiles of 16 x 16 windows. */
+size_t pnerf_image_metrics_workspace_bytes(int H, int W, int win);     /* run/evaluate.py:55-61,76; utils/visualizer.py:58-59; 0 for invalid or unsupported sizes */
+int pnerf_image_metrics(const float *d_img, const float *d_gt, int H, int W, int win, double data_range, int quantize8, double *d_out4,
+                        void *d_ws, size_t ws_bytes, void *stream);
+
 /* ---- diagnostics: ONE v_mfma_f32_32x32x16_f16, D = A B with caller-built fragments: d_a / d_b [64 lanes][8] f16 (lane l holds
  * A[l & 31][8 (l >> 5) .. + 7] resp. B[8 (l >> 5) .. + 7][l & 31]), d_out [64 lanes][16] f32 (register r of lane l =
  * D[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31]).  The tests pin with it the fragment layout and the un-flushed handling of f16

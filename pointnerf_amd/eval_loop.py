@@ -5,6 +5,7 @@
 Differences in HOW: the reference renders <= 48^2 = 2304 rays per call (278 calls, 278 voxel-grid rebuilds and a
 device->host copy of every chunk for an 800^2 image); here a chunk is as large as the dense query buffers allow
 (default 160 000 rays: 4 calls per 800^2 image), the grid is built once, and the canvas and the PSNR stay on the device.
+``image_scores`` is the device form of run/evaluate.py's report_metrics (PSNR / SSIM / RMSE of the 8-bit images).
 """
 import math
 
@@ -60,8 +61,39 @@ def psnr(img, gt):
     return -10.0 * torch.log10(mse)
 
 
+SCORE_NAMES = ("psnr", "ssim", "rmse")
+
+
 @torch.no_grad()
-def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, on_view=None):
+def image_scores(img, gt, metrics=SCORE_NAMES, quantize8=True, data_range=2.0):
+    """The scores of ``report_metrics`` (run/evaluate.py:55-61,76) for one [H, W, 3] float32 device image against its ground truth, as a
+    dict of 0-d float64 device tensors under the names ``scores.txt`` uses; no host read.  ``quantize8`` scores what the reference
+    scores: the images after the 8-bit PNG round trip of utils/visualizer.py:58-59, ``uint8(clip(x, 0, 1) * 255) / 255``.
+
+    psnr = 10 log10(1 / mse) and rmse = sqrt(mse); ssim = ``compare_ssim(gt, img, 11, multichannel=True)``.  The reference passes float
+    images and no data_range: skimage's PSNR takes range 1 for non-negative float images while its SSIM (<= 0.18, the versions that accept
+    the call) takes the float dtype range, 2.  That inconsistency is kept: ``data_range`` is the SSIM's and defaults to 2, PSNR always uses 1.
+    Names outside psnr / ssim / rmse raise NotImplementedError as the reference does; lpips / vgglpips do too, naming the weights they lack."""
+    from . import ops
+    check_score_names(metrics)
+    both = ops.image_metrics(img, gt.to(img.device), win=11, data_range=data_range, quantize8=quantize8)
+    mse = both[0]
+    value = {"psnr": lambda: 10.0 * torch.log10(1.0 / mse), "ssim": lambda: both[1], "rmse": lambda: torch.sqrt(mse)}
+    return {key: value[key]() for key in metrics}
+
+
+def check_score_names(metrics):
+    """NotImplementedError for a name ``image_scores`` does not compute (run/evaluate.py:76; lpips / vgglpips: no weights here)"""
+    for key in metrics:
+        if key in ("lpips", "vgglpips"):
+            raise NotImplementedError("metrics of %s not implemented: LPIPS needs the pretrained %s weights of the lpips package, which this "
+                                      "library does not ship" % (key, "AlexNet" if key == "lpips" else "VGG"))
+        if key not in SCORE_NAMES:
+            raise NotImplementedError("metrics of {} not implemented".format(key))
+
+
+@torch.no_grad()
+def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, on_view=None, metrics=()):
     """``test()`` of the training / evaluation scripts (run/train_ft.py:252-414, run/test_ft.py:134-274) around the model
     shell: for every ``test_num_step``-th view render all its rays through ``model.set_input / model.test()``, scatter the
     visuals into H x W canvases by ``pixel_idx``, score the items of ``opt.test_color_loss_items``
@@ -71,12 +103,18 @@ def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, 
 
     Returns (psnr of ``opt.test_color_loss_items[0]`` averaged over the views -- the function's return value in the
     reference --, {item: mean loss, item + "_psnr": mean psnr}).  Canvases stay on the device; ``on_view(i, visuals)`` receives
-    them (the reference writes PNGs there and afterwards re-reads them for SSIM / LPIPS, which need third-party packages and
-    are outside this path).  The chunk is 160 000 rays instead of <= 48^2."""
+    them (the reference writes PNGs there and afterwards re-reads them for PSNR / SSIM / RMSE -- ``metrics`` below -- and LPIPS,
+    which needs pretrained network weights and is outside this path).  The chunk is 160 000 rays instead of <= 48^2.
+
+    ``metrics`` (default none: the result is what it was without the keyword) names scores of ``image_scores``: each view's
+    ``coarse_raycolor`` canvas is scored against its ``gt_image`` canvas on the device, and the means over the views are added to the
+    returned dict under "psnr" / "ssim" / "rmse", the keys of the reference's ``report_metrics`` (run/evaluate.py:76).  They are read back
+    once, after the last view."""
+    check_score_names(metrics)                       # before any view is rendered
     model.eval()
     dev = model.device
     items = list(getattr(opt, "test_color_loss_items", ["coarse_raycolor"]))
-    acc, count = {}, 0
+    acc, count, scores = {}, 0, {}
     for i in range(0, len(views), test_num_step):
         view = views[i]
         raydir = view["raydir"].to(dev)
@@ -116,9 +154,15 @@ def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, 
         for kk, vv in losses.items():
             acc[kk] = acc.get(kk, 0) + vv
             acc[kk + "_psnr"] = acc.get(kk + "_psnr", 0) + (-10.0 * torch.log(vv) / math.log(10.0))
+        if metrics:
+            for kk, vv in image_scores(visuals["coarse_raycolor"].float().contiguous(), visuals["gt_image"], metrics=metrics).items():
+                scores[kk] = scores[kk] + vv if kk in scores else vv
         count += 1
         if on_view is not None:
             on_view(i, visuals)
     avg = {k: float(v) / max(count, 1) for k, v in acc.items()}
+    if scores:
+        host = torch.stack([scores[k] for k in scores]).cpu()            # the one host read of the scores, after all views
+        avg.update({k: float(host[j]) / max(count, 1) for j, k in enumerate(scores)})
     return avg.get(items[0] + "_psnr"), avg
 

@@ -552,6 +552,41 @@ def cross_terms_state():
     return bits, (mask if bits == 8 else 0)
 
 
+# ------------------------------------------------------------------------------------------ evaluation scores
+def image_metrics_sums(img, gt, win=11, data_range=2.0, quantize8=True):
+    """pnerf_image_metrics on two [H, W, 3] float32 contiguous device images: float64 device tensor [sum of squared differences,
+    SSIM-map sum of channel 0, 1, 2 over the (H - win + 1) x (W - win + 1) windows inside the image].  Enqueues only (no host read).
+    Anything that is not exactly that layout raises: a float64 image or an [H, W, 4] one would otherwise be read as something else."""
+    for name, t in (("img", img), ("gt", gt)):
+        _need_cuda(t, name)
+        if t.dtype != torch.float32:
+            raise TypeError("pointnerf_amd: image_metrics needs float32 images, %s is %s" % (name, t.dtype))
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("pointnerf_amd: image_metrics needs [H, W, 3] images, %s is %s" % (name, list(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("pointnerf_amd: image_metrics needs contiguous images, %s has strides %s" % (name, list(t.stride())))
+    if img.shape != gt.shape or img.device != gt.device:
+        raise ValueError("pointnerf_amd: image_metrics: img %s on %s and gt %s on %s differ" % (list(img.shape), img.device, list(gt.shape), gt.device))
+    H, W = int(img.shape[0]), int(img.shape[1])
+    lib = L.lib()
+    nbytes = lib.pnerf_image_metrics_workspace_bytes(H, W, int(win))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=img.device)
+    out4 = torch.empty(4, dtype=torch.float64, device=img.device)
+    L.check(lib.pnerf_image_metrics(_ptr(img.detach()), _ptr(gt.detach()), H, W, int(win), float(data_range), 1 if quantize8 else 0,
+                                    _ptr(out4), _ptr(ws), nbytes, _stream()), "pnerf_image_metrics")
+    return out4
+
+
+def image_metrics(img, gt, win=11, data_range=2.0, quantize8=True):
+    """float64 device tensor [mse, ssim] of two [H, W, 3] float32 device images the way run/evaluate.py scores them (compare_ssim(gt, img,
+    11, multichannel=True) of skimage <= 0.18 on float images: data_range 2; quantize8: through the 8-bit PNG round trip first).  No host
+    read: the two divisions by the element / window counts are device operations on the kernel's sums."""
+    out4 = image_metrics_sums(img, gt, win, data_range, quantize8)
+    H, W = int(img.shape[0]), int(img.shape[1])
+    n_win = (H - int(win) + 1) * (W - int(win) + 1)
+    return torch.stack([out4[0] / float(H * W * 3), out4[1:].sum() / float(3 * n_win)])
+
+
 # ------------------------------------------------------------------------------------------ profiling
 def mfma_rate_tflops(mode=2, ms_target=60.0, device=None):
     """TFLOP/s of register-resident v_mfma_f32_32x32x16_f16 on the whole chip (pnerf_debug_mfma_rate; mode 0 zero operands, 1 one constant,
