@@ -117,7 +117,7 @@ int pnerf_zero_one_backward(const float *d_conf, int n_points, const int32_t *d_
                             const float *d_gscale, float *d_grad_conf, void *stream);
 /* the same over the DENSE neighbor table d_idx [R][slots_per_ray] of a query, restricted to the rays with d_ray_hit[r] > 0 (the reference's
  * conf_coefficient exists for the hit rays only): no [R'', SR, K] copy of the table is made.  d_partial holds pnerf_zero_one_blocks(R * 256)
- * floats; the caller divides by (hit rays) x slots_per_ray. */
+ * floats; the caller divides by (hit rays) x slots_per_ray.  (One kernel pair serves both forms: the flat list is rows of 256 slots without hit flags.) */
 int pnerf_zero_one_forward_rays(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_ray_hit, int R, int slots_per_ray, float eps,
                                 float *d_partial, void *stream);
 int pnerf_zero_one_backward_rays(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_ray_hit, int R, int slots_per_ray, float eps,

@@ -47,14 +47,6 @@ struct BwdXArgs : BwdArgs {
 template <bool XYZG> struct BwdArgsOf { using T = BwdArgs; };
 template <> struct BwdArgsOf<true> { using T = BwdXArgs; };
 
-// d/d conf of log(v) + log(1 - v), v = clamp(clamp(conf, 1e-4, 1), eps, 1 - eps) with a straight-through inner clamp (the arithmetic of
-// render.hip pn_zero_one_value / k_zero_one_backward_rays), times the caller's scale
-__device__ __forceinline__ float pn_zero_one_grad(float conf, float eps, float gs) {
-    const float c = fminf(fmaxf(conf, 1e-4f), 1.0f);
-    if (!(c >= eps && c <= 1.f - eps)) return 0.f;
-    return gs * (1.f / c - 1.f / (1.f - c));
-}
-
 __device__ __forceinline__ void rot3b(const float *M, float x, float y, float z, bool transpose, float &ox, float &oy, float &oz) {
     if (!transpose) { ox = x * M[0] + y * M[3] + z * M[6]; oy = x * M[1] + y * M[4] + z * M[7]; oz = x * M[2] + y * M[5] + z * M[8]; }
     else { ox = x * M[0] + y * M[1] + z * M[2]; oy = x * M[3] + y * M[4] + z * M[5]; oz = x * M[6] + y * M[7] + z * M[8]; }
@@ -429,7 +421,7 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
                 const float alpha = pn_softplus_b(x), sg = pn_sigmoid_b(x);
                 const int rp = prow[r];
                 // w = wn * clamp(conf) with a straight-through clamp (gradiant_clamp, point_aggregators.py:722-724)
-                if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * invS + (a.zo_gs ? pn_zero_one_grad(zo_conf, a.zo_eps, a.zo_gs[0]) : 0.f));
+                if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * invS + (a.zo_gs ? PnZeroOne(zo_conf, a.zo_eps).grad(a.zo_gs[0]) : 0.f));
                 if (XG && rp >= 0) gw = dsg[r] * alpha + dotf;
                 dr = dsg[r] * wrow[r] * sg;
             }
@@ -1379,7 +1371,7 @@ __global__ void k_zero_one_empty(const float *__restrict__ conf, const int *__re
                                  float *__restrict__ g_conf) {
     const long long n_empty = (long long)counters[1] * slots_per_ray - (long long)counters[3];
     if (n_empty <= 0) return;
-    const float g = pn_zero_one_grad(conf[0], eps, gs[0]);
+    const float g = PnZeroOne(conf[0], eps).grad(gs[0]);
     if (g != 0.f) atomicAdd(&g_conf[0], g * (float)n_empty);
 }
 }  // namespace

@@ -46,6 +46,23 @@ int pn_exclusive_scan_i32(const int *in, int *out, long long n, int *scratch, hi
 // list = ascending indices i with in[i] > 0 ; *count_out = their number
 int pn_compact_gt0_i32(const int *in, long long n, int *list, int *count_out, int *scratch, hipStream_t s);
 
+// ---- the zero-one regulariser on one neighbor slot's confidence: THE definition of its arithmetic ----------------------------------
+// conf_coefficient = gradient_clamp(points_conf[clamp(sample_pidx, min=0)], 1e-4, 1) (point_aggregators.py:722-724, 812), loss_zero_one's term
+// log(v) + log(1 - v), v = clamp(conf_coefficient, eps, 1 - eps) (base_rendering_model.py:630-641).  Used by the regulariser's own passes
+// (render.hip) and by the render backward that carries its conf gradient (backward.hip: k_agg_backward, k_zero_one_empty).
+__device__ __forceinline__ int pn_zero_one_point(int p, int n) { return p < 0 ? 0 : (p >= n ? n - 1 : p); }       // an empty slot (-1) reads point 0
+struct PnZeroOne {
+    float c, eps;            // c: the gradient_clamp'ed confidence (clamp forward, identity backward)
+    __device__ __forceinline__ PnZeroOne(float conf, float eps_) : c(fminf(fmaxf(conf, 1e-4f), 1.0f)), eps(eps_) {}
+    __device__ __forceinline__ bool inside() const { return c >= eps && c <= 1.f - eps; }       // torch.clamp's backward mask (bounds included)
+    __device__ __forceinline__ float value() const {
+        const float v = fminf(fmaxf(c, eps), 1.f - eps);
+        return logf(v) + logf(1.f - v);
+    }
+    // d value / d conf times the caller's scale; where the mask holds v == c exactly
+    __device__ __forceinline__ float grad(float gs) const { return inside() ? gs * (1.f / c - 1.f / (1.f - c)) : 0.f; }
+};
+
 // ---- device view of the voxel grid (grid.hip builds it, query.hip walks it) ----------------
 struct PnGridDev {
     float ox, oy, oz;        // grid origin (ranges[0..2])

@@ -249,20 +249,18 @@ __global__ __launch_bounds__(TPB) void k_scatter_add_rows(const float *__restric
 // in ATen.  Here: one pass that sums the terms per block (the caller adds the per-block partials: deterministic), one pass that
 // adds  g * (1 / v - 1 / (1 - v)) [eps <= c' <= 1 - eps]  into the confidence gradient, with the point-0 flood of the empty slots
 //  reduced per block first.
-__device__ __forceinline__ float pn_zero_one_value(const float *__restrict__ conf, int n, int p, float eps, bool &inside) {
-    p = p < 0 ? 0 : (p >= n ? n - 1 : p);
-    const float c = fminf(fmaxf(conf[p], 1e-4f), 1.0f);         // gradient_clamp: clamp forward, identity backward
-    inside = c >= eps && c <= 1.f - eps;                        // torch.clamp's backward mask (bounds included)
-    return fminf(fmaxf(c, eps), 1.f - eps);
-}
-__global__ __launch_bounds__(TPB) void k_zero_one_forward(const float *__restrict__ conf, int n, const int *__restrict__ idx, long long n_idx, float eps,
-                                                          float *__restrict__ partial) {
+// One forward and one backward kernel over rows x slots elements of the index table, a workgroup per row at a time.  The rays form: rows = R,
+// slots = SR * K, hit = the per-ray hit flags (only rays that hit the cloud count: the reference forms conf_coefficient for the R'' hit rays
+// only; no [R'', SR, K] copy of the table is ever made).  The flat form: rows of TPB elements, hit = NULL, `total` cuts the last row short.
+__global__ __launch_bounds__(TPB) void k_zero_one_forward(const float *__restrict__ conf, int n, const int *__restrict__ idx, const int *__restrict__ hit, long long rows, int slots,
+                                                          long long total, float eps, float *__restrict__ partial) {
     __shared__ float red[TPB / 64];
     float acc = 0.f;
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < n_idx; e += (long long)gridDim.x * TPB) {
-        bool inside;
-        const float v = pn_zero_one_value(conf, n, idx[e], eps, inside);
-        acc += logf(v) + logf(1.f - v);
+    for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+        if (hit && hit[r] <= 0) continue;
+        const int *row = idx + r * slots;
+        const int m = (int)(total - r * slots < slots ? total - r * slots : slots);
+        for (int e = threadIdx.x; e < m; e += TPB) acc += PnZeroOne(conf[pn_zero_one_point(row[e], n)], eps).value();
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
@@ -274,71 +272,23 @@ __global__ __launch_bounds__(TPB) void k_zero_one_forward(const float *__restric
         partial[blockIdx.x] = t;
     }
 }
-__global__ __launch_bounds__(TPB) void k_zero_one_backward(const float *__restrict__ conf, int n, const int *__restrict__ idx, long long n_idx, float eps,
-                                                           const float *__restrict__ gscale, float *__restrict__ grad_conf) {
+__global__ __launch_bounds__(TPB) void k_zero_one_backward(const float *__restrict__ conf, int n, const int *__restrict__ idx, const int *__restrict__ hit, long long rows, int slots,
+                                                           long long total, float eps, const float *__restrict__ gscale, float *__restrict__ grad_conf) {
     __shared__ float row0;
     if (threadIdx.x == 0) row0 = 0.f;
     __syncthreads();
     const float gs = gscale[0];
     float mine0 = 0.f;
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < n_idx; e += (long long)gridDim.x * TPB) {
-        const int p = idx[e];
-        bool inside;
-        const float v = pn_zero_one_value(conf, n, p, eps, inside);
-        if (!inside) continue;
-        const float g = gs * (1.f / v - 1.f / (1.f - v));
-        if (p <= 0) mine0 += g;
-        else atomicAdd(&grad_conf[p >= n ? n - 1 : p], g);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine0 += __shfl_xor(mine0, off, 64);
-    if ((threadIdx.x & 63) == 0 && mine0 != 0.f) atomicAdd(&row0, mine0);
-    __syncthreads();
-    if (threadIdx.x == 0 && row0 != 0.f) atomicAdd(&grad_conf[0], row0);
-}
-// the same two passes over the DENSE neighbor table [R][slots] with the per-ray hit flags: only rays that hit the cloud count (the reference
-// forms conf_coefficient for the R'' hit rays only).  One workgroup per ray at a time: no [R'', SR, K] copy of the table is ever made.
-__global__ __launch_bounds__(TPB) void k_zero_one_forward_rays(const float *__restrict__ conf, int n, const int *__restrict__ idx, const int *__restrict__ hit, int R, int slots,
-                                                               float eps, float *__restrict__ partial) {
-    __shared__ float red[TPB / 64];
-    float acc = 0.f;
-    for (int r = blockIdx.x; r < R; r += gridDim.x) {
-        if (hit[r] <= 0) continue;
-        const int *row = idx + (long long)r * slots;
-        for (int e = threadIdx.x; e < slots; e += TPB) {
-            bool inside;
-            const float v = pn_zero_one_value(conf, n, row[e], eps, inside);
-            acc += logf(v) + logf(1.f - v);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
-        partial[blockIdx.x] = t;
-    }
-}
-__global__ __launch_bounds__(TPB) void k_zero_one_backward_rays(const float *__restrict__ conf, int n, const int *__restrict__ idx, const int *__restrict__ hit, int R, int slots,
-                                                                float eps, const float *__restrict__ gscale, float *__restrict__ grad_conf) {
-    __shared__ float row0;
-    if (threadIdx.x == 0) row0 = 0.f;
-    __syncthreads();
-    const float gs = gscale[0];
-    float mine0 = 0.f;
-    for (int r = blockIdx.x; r < R; r += gridDim.x) {
-        if (hit[r] <= 0) continue;
-        const int *row = idx + (long long)r * slots;
-        for (int e = threadIdx.x; e < slots; e += TPB) {
-            const int p = row[e];
-            bool inside;
-            const float v = pn_zero_one_value(conf, n, p, eps, inside);
-            if (!inside) continue;
-            const float g = gs * (1.f / v - 1.f / (1.f - v));
-            if (p <= 0) mine0 += g;
-            else atomicAdd(&grad_conf[p >= n ? n - 1 : p], g);
+    for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+        if (hit && hit[r] <= 0) continue;
+        const int *row = idx + r * slots;
+        const int m = (int)(total - r * slots < slots ? total - r * slots : slots);
+        for (int e = threadIdx.x; e < m; e += TPB) {
+            const int p = pn_zero_one_point(row[e], n);
+            const PnZeroOne z(conf[p], eps);
+            if (!z.inside()) continue;
+            if (p == 0) mine0 += z.grad(gs);
+            else atomicAdd(&grad_conf[p], z.grad(gs));
         }
     }
 #pragma unroll
@@ -399,43 +349,40 @@ extern "C" int pnerf_color_loss_backward_rays(const float *d_ray_color, const fl
     return 0;
 }
 
+extern "C" int pnerf_zero_one_blocks(int64_t n_idx) {
+    const long long b = (n_idx + TPB - 1) / TPB;
+    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+}
+// both passes of both forms: rows x slots elements of d_idx (`total` of them exist), d_hit optional; the caller has checked its arguments
+static int pn_zero_one_launch(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_hit, long long rows, int slots, long long total, float eps,
+                              float *d_partial, const float *d_gscale, float *d_grad_conf, void *stream) {
+    const dim3 grid(pnerf_zero_one_blocks(rows * TPB));
+    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
+    if (d_partial) hipLaunchKernelGGL(k_zero_one_forward, grid, dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, d_hit, rows, slots, total, eps, d_partial);
+    else hipLaunchKernelGGL(k_zero_one_backward, grid, dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, d_hit, rows, slots, total, eps, d_gscale, d_grad_conf);
+    PN_CHECK_LAUNCH();
+    return 0;
+}
 extern "C" int pnerf_zero_one_forward_rays(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_ray_hit, int R, int slots_per_ray, float eps,
                                            float *d_partial, void *stream) {
     if (!d_conf || !d_partial || !d_idx || !d_ray_hit || n_points <= 0 || R < 0 || slots_per_ray <= 0) return PNERF_E_INVAL;
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_zero_one_forward_rays, dim3(pnerf_zero_one_blocks((int64_t)R * TPB)), dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, d_ray_hit, R, slots_per_ray, eps, d_partial);
-    PN_CHECK_LAUNCH();
-    return 0;
+    return pn_zero_one_launch(d_conf, n_points, d_idx, d_ray_hit, R, slots_per_ray, (long long)R * slots_per_ray, eps, d_partial, nullptr, nullptr, stream);
 }
 extern "C" int pnerf_zero_one_backward_rays(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_ray_hit, int R, int slots_per_ray, float eps,
                                             const float *d_gscale, float *d_grad_conf, void *stream) {
     if (R == 0) return 0;
     if (!d_conf || !d_idx || !d_ray_hit || !d_gscale || !d_grad_conf || n_points <= 0 || R < 0 || slots_per_ray <= 0) return PNERF_E_INVAL;
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_zero_one_backward_rays, dim3(pnerf_zero_one_blocks((int64_t)R * TPB)), dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, d_ray_hit, R, slots_per_ray, eps, d_gscale, d_grad_conf);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pnerf_zero_one_blocks(int64_t n_idx) {
-    const long long b = (n_idx + TPB - 1) / TPB;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+    return pn_zero_one_launch(d_conf, n_points, d_idx, d_ray_hit, R, slots_per_ray, (long long)R * slots_per_ray, eps, nullptr, d_gscale, d_grad_conf, stream);
 }
 extern "C" int pnerf_zero_one_forward(const float *d_conf, int n_points, const int32_t *d_idx, int64_t n_idx, float eps, float *d_partial, void *stream) {
     if (!d_conf || !d_partial || n_points <= 0 || n_idx < 0 || (n_idx > 0 && !d_idx)) return PNERF_E_INVAL;
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_zero_one_forward, dim3(pnerf_zero_one_blocks(n_idx)), dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, (long long)n_idx, eps, d_partial);
-    PN_CHECK_LAUNCH();
-    return 0;
+    return pn_zero_one_launch(d_conf, n_points, d_idx, nullptr, (n_idx + TPB - 1) / TPB, TPB, n_idx, eps, d_partial, nullptr, nullptr, stream);
 }
 extern "C" int pnerf_zero_one_backward(const float *d_conf, int n_points, const int32_t *d_idx, int64_t n_idx, float eps, const float *d_gscale,
                                        float *d_grad_conf, void *stream) {
     if (n_idx == 0) return 0;
     if (!d_conf || !d_idx || !d_gscale || !d_grad_conf || n_points <= 0 || n_idx < 0) return PNERF_E_INVAL;
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_zero_one_backward, dim3(pnerf_zero_one_blocks(n_idx)), dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, (long long)n_idx, eps, d_gscale, d_grad_conf);
-    PN_CHECK_LAUNCH();
-    return 0;
+    return pn_zero_one_launch(d_conf, n_points, d_idx, nullptr, (n_idx + TPB - 1) / TPB, TPB, n_idx, eps, nullptr, d_gscale, d_grad_conf, stream);
 }
 
 extern "C" int pnerf_gather_rows(const float *d_src, int n_src, int width, const int32_t *d_idx, int64_t n_idx, float *d_dst, void *stream) {

@@ -8,6 +8,8 @@ replaces the reference's ``neural_points(...) -> aggregator(...) -> ray_dist -> 
 neural_points.py:132; every reference script leaves it 0): the backward then also forms d xyz through the distance encoding and the
 inverse-distance weights (k_agg_backward's XYZG instances), and returns it in the same point-gradient bucket.
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -59,7 +61,6 @@ class FusedRender(torch.autograd.Function):
         pts = ops.make_points(env["xyz"], *ctx.point_arrays)
         # a step whose saved activations would exceed the arena budget runs its forward without saving anything; the backward then
         # re-runs the forward chunk of rays by chunk of rays (ops.arena_budget_bytes)
-        from . import _lib as L
         ctx.recompute = bool(env["train"]) and L.lib().pnerf_agg_saved_bytes(env["n_valid"], env["K"]) > ops.arena_budget_bytes()
         fwd = ops.render_forward(env["cam"], pts, env["packed"], env["flat"], env["raydir"], env["dense"],
                                  env["R"], env["SR"], env["K"], env["n_valid"], env["train"] and not ctx.recompute)
@@ -71,19 +72,13 @@ class FusedRender(torch.autograd.Function):
         ctx.shapes = (tuple(emb.shape), tuple(conf.shape), tuple(pdir.shape), tuple(color.shape))
         ctx.n_mlp = len(mlp_params)
         # env["zero_one_eps"] (training): the numerator of the zero-one regulariser on the hit rays' conf_coefficient is a SEVENTH, differentiable
-        # output of this node (one pass over the dense neighbor table, pnerf_zero_one_forward_rays), so that its conf gradient can ride on
+        # output of this node (one pass over the dense neighbor table, ops.zero_one_sum), so that its conf gradient can ride on
         # the conf atomics of this node's backward instead of repeating ~7 M atomics on the same addresses in a pass of its own
         ctx.zo = None
         zo_sum = None
         if env["train"] and env.get("zero_one_eps") is not None:
-            lib = L.lib()
-            dense, cflat = env["dense"], ctx.point_arrays[1].reshape(-1)
-            R_, slots = env["R"], env["SR"] * env["K"]
-            part = torch.empty(lib.pnerf_zero_one_blocks(R_ * 256), dtype=torch.float32, device=cflat.device)
-            L.check(lib.pnerf_zero_one_forward_rays(ops._ptr(cflat), cflat.numel(), ops._ptr(dense["sample_pidx"]), ops._ptr(dense["ray_hit"]), R_, slots,
-                                                    float(env["zero_one_eps"]), ops._ptr(part), ops._stream()), "pnerf_zero_one_forward_rays")
-            zo_sum = part.sum()
             ctx.zo = float(env["zero_one_eps"])
+            zo_sum = ops.zero_one_sum(ctx.point_arrays[1].reshape(-1), env["dense"]["sample_pidx"], env["dense"]["ray_hit"], ctx.zo)
         # ONE call (a second one replaces the set): every output the backward does not differentiate.  decoded / weight / opacity are kept in
         # ctx.fwd -- were they differentiable outputs, node -> ctx.fwd -> tensor -> grad_fn = node would be a reference cycle that holds the
         # activation arena of every training forward that is never back-propagated
@@ -134,10 +129,7 @@ class FusedRender(torch.autograd.Function):
             zo = None
         if zo is not None:
             # (no valid sample at all, or the chunk-by-chunk recompute whose chunks carry their own counters: the regulariser's own pass)
-            dense, cflat = env["dense"], ctx.point_arrays[1].reshape(-1)
-            L.check(L.lib().pnerf_zero_one_backward_rays(ops._ptr(cflat), cflat.numel(), ops._ptr(dense["sample_pidx"]), ops._ptr(dense["ray_hit"]), env["R"],
-                                                         env["SR"] * env["K"], zo[1], ops._ptr(zo[0]), ops._ptr(grads["points_conf"].reshape(-1)), ops._stream()),
-                    "pnerf_zero_one_backward_rays")
+            ops.zero_one_add_grad(ctx.point_arrays[1].reshape(-1), env["dense"]["sample_pidx"], env["dense"]["ray_hit"], zo[1], zo[0], grads["points_conf"].reshape(-1))
         FusedRender.point_grads_ready = ev
         # what the early all-reduce may touch: exactly the tensors this backward wrote (dist.allreduce_grads checks p.grad against them)
         FusedRender.point_grad_ptrs = {grads[n].data_ptr() for n in names}
@@ -159,7 +151,6 @@ def _backward_in_chunks(env, pts, g_color, gflat, grads, ev):
     """Backward of a render step whose saved activations do not fit the arena budget: for consecutive runs of rays, re-run the
     training forward (its saved activations within the budget) and the backward; gradients accumulate in the same buffers.
     One host synchronisation per chunk (its number of valid samples sizes its arena)."""
-    from . import _lib as L
     lib = L.lib()
     dense, R, SR, K = env["dense"], env["R"], env["SR"], env["K"]
     budget = ops.arena_budget_bytes()
@@ -207,8 +198,6 @@ class Aggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, env, emb, conf, pdir, color, *mlp_params):
         # env: dict(cam, xyz_slots [N',3], xyz_pers [N',3], loc_w, loc_pers, raydir [R,3], pidx, nn, R, SR, K, flat, packed, train, layout)
-        import ctypes
-        from . import _lib as L
         lib = L.lib()
         dev = emb.device
         R, SR, K = env["R"], env["SR"], env["K"]
@@ -240,8 +229,6 @@ class Aggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_decoded, *unused):
-        import ctypes
-        from . import _lib as L
         lib = L.lib()
         env = ctx.env
         vlist, counters, saved, decoded, weight, n_valid = ctx.keep

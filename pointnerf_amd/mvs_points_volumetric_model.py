@@ -31,6 +31,7 @@ from torch import nn
 from torch.optim import lr_scheduler
 
 from . import dist as pdist
+from . import losses
 from .neural_points import NeuralPoints
 from .neural_points_volumetric_model import NeuralPointsRayMarching, fill_invalid
 from .optim import FusedAdam
@@ -141,7 +142,7 @@ class MvsPointsVolumetricModel:
                                                         num_viewdir_freqs=getattr(opt, "num_viewdir_freqs", 0)).to(self.device)
         if self.device.type == "cuda":
             self.aggregator.flatten_()
-            self.net_ray_marching.fused_zero_one = True      # compute_losses takes the fused zero-one pass (ops.ZeroOneConf)
+            self.net_ray_marching.fused_zero_one = True      # compute_losses takes the fused zero-one forms (losses.zero_one)
             # the colour loss over the renderer's DENSE ray colours (ops.ColorLossRays; no compaction of the hit rays, no scatter back): taken when
             # every colour-loss item that carries a gradient is a ray_masked one -- the lego script's items are (ray_masked 1.0, ray_miss 0.0,
             # full image 0.0); ray_miss predicts the constant background and has no gradient, a full-image item with a non-zero weight would
@@ -280,36 +281,29 @@ class MvsPointsVolumetricModel:
         opt, out, W = self.opt, self.output, pdist.world()
         dev = out["coarse_raycolor"].device
         hit = out["ray_mask"][0] > 0
-        hidx = out.get("_hit_index")                      # hit-ray indices from the renderer: indexing without a synchronisation
         dense = out.get("_dense_color")                   # fused colour loss (training steps): (dense ray colours, hit flags, number of hit rays)
+        raw = out if dense is not None else self._raw     # the renderer's own dict, for the item that carries the gradient
         self.loss_total = 0
         for i, name in enumerate(opt.color_loss_items):
-            if dense is not None:
-                # every item from the dense per-ray tensors, no boolean-mask index (each is a device -> host synchronisation): the ray_masked
-                # item through the fused pass (it carries the gradient), the others from the filled image (no gradient: see create_network_models)
-                from . import ops
-                if name == "ray_masked_coarse_raycolor":
-                    n = pdist.global_counts(3 * dense[2], device=dev)[0]
-                    loss = ops.color_loss_sum_rays(dense[0], self.gt_image[0], dense[1]) / pdist.at_least_one(n)
-                else:
-                    with torch.no_grad():
-                        key = name[len("ray_miss") + 1:] if name.startswith("ray_miss") else (name[len("ray_masked") + 1:] if name.startswith("ray_masked") else name)
-                        sq = (out[key][0] - self.gt_image[0]) ** 2
-                        if name.startswith("ray_miss"):
-                            loss = (sq * torch.logical_not(hit)[:, None]).sum() / 3.0
-                        elif name.startswith("ray_masked"):
-                            n = pdist.global_counts(3 * dense[2], device=dev)[0]
-                            loss = (sq * hit[:, None]).sum() / pdist.at_least_one(n)
-                        else:
-                            n = pdist.global_counts(sq.numel(), device=dev)[0]
-                            loss = sq.sum() / pdist.at_least_one(n)
-                self.loss_total = self.loss_total + (loss * opt.color_loss_weights[i] + 1e-6 / W)
-                setattr(self, "loss_" + name, loss)
-                continue
-            if name.startswith("ray_masked"):
-                key = name[len("ray_masked") + 1:]
-                pred = self._raw[key][0] if (self._raw is not None and key == "coarse_raycolor") else out[key][0][hit]
-                gt = self.gt_image[0].index_select(0, hidx) if hidx is not None else self.gt_image[0][hit]
+            if name == "ray_masked_coarse_raycolor" and raw is not None:
+                s, count = losses.masked_color(raw, self.gt_image)
+                loss = s / pdist.at_least_one(pdist.global_counts(count, device=dev)[0])
+            elif dense is not None:
+                # every other item from the dense per-ray tensors, no boolean-mask index (each is a device -> host synchronisation), from the
+                # filled image (no gradient: see create_network_models)
+                with torch.no_grad():
+                    key = name[len("ray_miss") + 1:] if name.startswith("ray_miss") else (name[len("ray_masked") + 1:] if name.startswith("ray_masked") else name)
+                    sq = (out[key][0] - self.gt_image[0]) ** 2
+                    if name.startswith("ray_miss"):
+                        loss = (sq * torch.logical_not(hit)[:, None]).sum() / 3.0
+                    elif name.startswith("ray_masked"):
+                        n = pdist.global_counts(3 * dense[2], device=dev)[0]
+                        loss = (sq * hit[:, None]).sum() / pdist.at_least_one(n)
+                    else:
+                        n = pdist.global_counts(sq.numel(), device=dev)[0]
+                        loss = sq.sum() / pdist.at_least_one(n)
+            elif name.startswith("ray_masked"):
+                pred, gt = out[name[len("ray_masked") + 1:]][0][hit], self.gt_image[0][hit]
                 n = pdist.global_counts(pred.numel(), device=dev)[0]
                 loss = ((pred - gt) ** 2).sum() / pdist.at_least_one(n)
             elif name.startswith("ray_miss"):
@@ -325,26 +319,10 @@ class MvsPointsVolumetricModel:
             self.loss_total = self.loss_total + (loss * opt.color_loss_weights[i] + 1e-6 / W)
             setattr(self, "loss_" + name, loss)
         for i, name in enumerate(opt.zero_one_loss_items):
-            if name == "conf_coefficient" and "_zero_one_sum" in out:  # fused into the render node (training steps)
-                zsum, count = out["_zero_one_sum"]
-                n = pdist.global_counts(count, device=dev)[0]
-                loss = zsum / pdist.at_least_one(n)
-                self.loss_total = self.loss_total + loss * opt.zero_one_loss_weights[i]
-                setattr(self, "loss_" + name, loss)
+            term = losses.zero_one(out, self.gt_image, opt.zero_epsilon, name)       # (the three forms of conf_coefficient; any other name: the tensor)
+            if term is None:
                 continue
-            if name == "conf_coefficient" and "_zero_one" in out:      # fused form (NeuralPointsRayMarching.fused_zero_one)
-                from . import ops
-                conf, pidx_dense, ray_hit, count = out["_zero_one"]
-                n = pdist.global_counts(count, device=dev)[0]
-                loss = ops.zero_one_conf_sum_rays(conf, pidx_dense, ray_hit, opt.zero_epsilon) / pdist.at_least_one(n)
-                self.loss_total = self.loss_total + loss * opt.zero_one_loss_weights[i]
-                setattr(self, "loss_" + name, loss)
-                continue
-            if name not in out:
-                continue
-            val = torch.clamp(out[name], opt.zero_epsilon, 1 - opt.zero_epsilon)
-            n = pdist.global_counts(val.numel(), device=dev)[0]
-            loss = (torch.log(val) + torch.log(1 - val)).sum() / pdist.at_least_one(n)
+            loss = term[0] / pdist.at_least_one(pdist.global_counts(term[1], device=dev)[0])
             self.loss_total = self.loss_total + loss * opt.zero_one_loss_weights[i]
             setattr(self, "loss_" + name, loss)
         for i, name in enumerate(opt.l2_size_loss_items):

@@ -30,8 +30,6 @@ def gradient_clamp(sampled_conf, lo=0.0001, hi=1.0):
 
 # PNERF_SPECULATE=0: every training step waits for its counters before it is enqueued (rounds 1-3)
 SPECULATE = os.environ.get("PNERF_SPECULATE", "1") != "0"
-# PNERF_ZERO_ONE_IN_RENDER=0 (dev A/B): the fused zero-one regulariser as its own forward / backward pass (round 3) instead of inside the render node
-ZERO_ONE_IN_RENDER = os.environ.get("PNERF_ZERO_ONE_IN_RENDER", "1") != "0"
 
 
 class NeuralPointsRayMarching(nn.Module):
@@ -63,9 +61,10 @@ class NeuralPointsRayMarching(nn.Module):
             self._pinned_words = torch.empty(n, dtype=torch.int64).pin_memory()
         return self._pinned_words
 
-    def render_dense(self, campos, raydir, camrotc2w, near, far, bg_color=None, train=None):
+    def render_dense(self, campos, raydir, camrotc2w, near, far, bg_color=None, train=None, zero_one_eps=None):
         """The fused step on all R rays.  Returns (ray_color [R,3], opacity, bg_trans, blend_w, decoded, weight, zo_sum, dense); zo_sum =
-        the zero-one regulariser's numerator over the hit rays' conf_coefficient when ``_zero_one_in_render()`` (else a constant 0)."""
+        the zero-one regulariser's numerator over the hit rays' conf_coefficient when a training step is given ``zero_one_eps`` (the
+        "render" form of ``_output_forms``; else a constant 0)."""
         opt, npnt, agg = self.opt, self.neural_points, self.aggregator
         train = torch.is_grad_enabled() if train is None else train
         # xyz_grad > 0: the point positions are a leaf of the fused step (d xyz from k_agg_backward's XYZG instances)
@@ -92,8 +91,8 @@ class NeuralPointsRayMarching(nn.Module):
         env = dict(cam=cam, xyz=npnt.xyz.detach().reshape(-1, 3).contiguous(), raydir=raydir.detach().reshape(-1, 3).contiguous().float(),
                    dense=dense, R=R, SR=int(opt.SR), K=int(opt.K), n_valid=0, flat=st.flat, packed=st.packed_image(),
                    train=bool(train), layout=layout, want_grad_event=bool(train) and raydir.is_cuda and pdist.active())
-        if train and self._zero_one_in_render():
-            env["zero_one_eps"] = float(getattr(opt, "zero_epsilon", 1e-3))
+        if train and zero_one_eps is not None:
+            env["zero_one_eps"] = float(zero_one_eps)
         if xyz_leaf:
             env["xyz_grad"] = True
         leaves = (npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + ((npnt.xyz,) if xyz_leaf else ()) + tuple(mlp_params)
@@ -130,20 +129,38 @@ class NeuralPointsRayMarching(nn.Module):
             out = FusedRender.apply(env, *leaves)
         return out + (dense,)
 
-    def _zero_one_in_render(self):
-        """the zero-one regulariser on conf_coefficient as part of the render node (``fused_zero_one`` callers whose only consumer of
-        conf_coefficient is that loss): its numerator is an output of the node, its conf gradient rides on the node's own conf atomics"""
-        opt = self.opt
-        return ZERO_ONE_IN_RENDER and bool(getattr(self, "fused_zero_one", False)) and opt.sparse_loss_weight <= 0 and getattr(opt, "prob", 0) == 0 \
-            and "conf_coefficient" in getattr(opt, "zero_one_loss_items", ())
+    def _output_forms(self):
+        """THE decision of one ``forward`` call, from the caller's flags and the options: (dense colours handed out?, form of the zero-one
+        regulariser on conf_coefficient).
+
+        ``fused_zero_one`` / ``fused_color_loss`` (ours; set by callers whose loss goes through dist.hot_path_loss, and by the model shell of this
+        package -- fused_color_loss when every colour-loss item with a non-zero weight is a ray_masked / ray_miss one, the lego script's setting:
+        MvsPointsVolumetricModel.create_network_models) say that the only consumer of conf_coefficient / of the rendered colours is the loss.
+        Zero-one forms: "render" -- a training step: the numerator is an output of the render node, its conf gradient rides on the node's own conf
+        atomics ("_zero_one_sum"); "pass" -- the same caller under no_grad: what the stand-alone fused pass needs, (points_conf, the DENSE neighbor
+        table, the rays' hit flags, number of conf_coefficient elements), no [R'', SR, K] copy of the table ("_zero_one", ops.zero_one_conf_sum_rays);
+        "tensor" -- weight / blend_weight / conf_coefficient [1, R'', SR, K] materialised like the reference (some other consumer: the sparse
+        loss, the probe outputs, a caller without the flag); None -- nobody reads them.
+        Dense colours: a TRAINING step gets the dense ray colours and the hit flags under "_dense_color" (ops.ColorLossRays: one pass forward, one
+        backward, d colour written for every ray) and the compacted [1, R'', ...] outputs are not formed -- no argsort, no index_selects, no
+        scatter-back in the backward (~25 launches per step)."""
+        opt, grad = self.opt, torch.is_grad_enabled()
+        loss_only = bool(getattr(self, "fused_zero_one", False)) and opt.sparse_loss_weight <= 0 and getattr(opt, "prob", 0) == 0
+        has_item = "conf_coefficient" in getattr(opt, "zero_one_loss_items", ())
+        if has_item and loss_only:
+            zero_one = "render" if grad else "pass"
+        else:
+            zero_one = "tensor" if (has_item or opt.sparse_loss_weight > 0 or getattr(opt, "prob", 0) != 0) else None
+        return bool(getattr(self, "fused_color_loss", False)) and grad and loss_only, zero_one
 
     def forward(self, campos, raydir, gt_image=None, bg_color=None, camrotc2w=None, pixel_idx=None, near=None, far=None,
                 focal=None, h=None, w=None, intrinsic=None, **kargs):
         opt = self.opt
         if "bg_ray" in kargs:
             bg_color = None
-        ray_color, opacity, bg_trans, blend_w, decoded, weight, zo_sum, dense = self.render_dense(campos, raydir, camrotc2w, near, far, bg_color)
-        zo_in_render = torch.is_grad_enabled() and self._zero_one_in_render()
+        dense_color, zero_one = self._output_forms()
+        ray_color, opacity, bg_trans, blend_w, decoded, weight, zo_sum, dense = self.render_dense(
+            campos, raydir, camrotc2w, near, far, bg_color, zero_one_eps=getattr(opt, "zero_epsilon", 1e-3) if zero_one == "render" else None)
         hit = dense["ray_hit"] > 0
         SR, K = int(opt.SR), int(opt.K)
         # Indices of the hit rays WITHOUT a host round trip: their number is already on the host (the counters the arena was
@@ -151,44 +168,25 @@ class NeuralPointsRayMarching(nn.Module):
         # synchronise once per tensor (nonzero), and the device would idle between forward, loss and backward while the
         # host catches up; with this the whole step is enqueued behind one synchronisation.
         n_hit = self.last_stats["rays_hit"]
-        # ``fused_color_loss`` (ours, like ``fused_zero_one`` below; set by callers whose loss goes through dist.hot_path_loss, and by the model
-        # shell of this package when every colour-loss item with a non-zero weight is a ray_masked / ray_miss one -- the lego script's
-        # setting: MvsPointsVolumetricModel.create_network_models): a TRAINING step whose only consumer of the rendered colours is the colour loss gets the dense ray colours and the
-        # hit flags under "_dense_color" (ops.ColorLossRays: one pass forward, one backward, d colour written for every ray) and the compacted
-        # [1, R'', ...] outputs are not formed -- no argsort, no index_selects, no scatter-back in the backward (~25 launches per step)
-        if getattr(self, "fused_color_loss", False) and torch.is_grad_enabled() and getattr(opt, "prob", 0) == 0 \
-                and opt.sparse_loss_weight <= 0 and getattr(self, "fused_zero_one", False):
+        if dense_color:
             output = {"_dense_color": (ray_color, dense["ray_hit"], n_hit), "ray_mask": hit.to(torch.int8)[None],
                       "_dense_aux": (opacity.detach(), bg_trans.detach())}       # (for fill_invalid's full-size visuals: references, no work)
-            if "conf_coefficient" in opt.zero_one_loss_items:
-                if zo_in_render:
-                    output["_zero_one_sum"] = (zo_sum, n_hit * SR * K)
-                else:
-                    output["_zero_one"] = (self.neural_points.points_conf, dense["sample_pidx"], dense["ray_hit"], n_hit * SR * K)
-            return output
-        idx = torch.argsort(dense["ray_hit"], descending=True, stable=True)[:n_hit]
-        take = lambda t: t.index_select(0, idx)
-        output = {"_hit_index": idx}
-        # queried_shading = not any(ray_valid) per ray (:322 of the reference): the R'' rays ARE the rays with a valid sample (ray_mask comes from
-        # the same neighbor table, query_worldcoords.cu:425-429), so it is identically zero -- no pass over the [R'', SR] counts
-        output["queried_shading"] = torch.zeros(1, n_hit, 3, dtype=torch.float32, device=ray_color.device)
-        output["coarse_raycolor"] = take(ray_color)[None]
-        output["coarse_point_opacity"] = take(opacity)[None]
-        output["coarse_is_background"] = take(bg_trans)[None, :, None]
-        output["ray_mask"] = hit.to(torch.int8)[None]
-        want_w = (opt.sparse_loss_weight > 0) or ("conf_coefficient" in opt.zero_one_loss_items) or getattr(opt, "prob", 0) != 0
-        # ``fused_zero_one`` (ours; set by callers whose loss goes through dist.hot_path_loss / the model shell of this package): when the
-        # only consumer of conf_coefficient is the zero-one regulariser, hand out what that loss needs -- (points_conf, the hit rays'
-        # neighbor table) under "_zero_one" -- instead of materialising weight / conf_coefficient [1, R'', SR, K] (ops.ZeroOneConf)
-        only_zero_one = getattr(self, "fused_zero_one", False) and opt.sparse_loss_weight <= 0 and getattr(opt, "prob", 0) == 0
-        if want_w and only_zero_one:
-            # (points_conf, the DENSE neighbor table, the rays' hit flags, number of conf_coefficient elements): the loss runs over the hit rays
-            # of the dense table in place (ops.ZeroOneConfRays) -- no [R'', SR, K] copy of it
-            if zo_in_render:        # (training: the numerator came out of the render node; evaluation under no_grad: the stand-alone pass)
-                output["_zero_one_sum"] = (zo_sum, n_hit * SR * K)
-            else:
-                output["_zero_one"] = (self.neural_points.points_conf, dense["sample_pidx"], dense["ray_hit"], n_hit * SR * K)
-        elif want_w:
+        else:
+            idx = torch.argsort(dense["ray_hit"], descending=True, stable=True)[:n_hit]
+            take = lambda t: t.index_select(0, idx)
+            output = {"_hit_index": idx}
+            # queried_shading = not any(ray_valid) per ray (:322 of the reference): the R'' rays ARE the rays with a valid sample (ray_mask comes from
+            # the same neighbor table, query_worldcoords.cu:425-429), so it is identically zero -- no pass over the [R'', SR] counts
+            output["queried_shading"] = torch.zeros(1, n_hit, 3, dtype=torch.float32, device=ray_color.device)
+            output["coarse_raycolor"] = take(ray_color)[None]
+            output["coarse_point_opacity"] = take(opacity)[None]
+            output["coarse_is_background"] = take(bg_trans)[None, :, None]
+            output["ray_mask"] = hit.to(torch.int8)[None]
+        if zero_one == "render":
+            output["_zero_one_sum"] = (zo_sum, n_hit * SR * K)
+        elif zero_one == "pass":
+            output["_zero_one"] = (self.neural_points.points_conf, dense["sample_pidx"], dense["ray_hit"], n_hit * SR * K)
+        elif zero_one == "tensor":                # (never together with the dense colours: those imply a caller that reads conf_coefficient for the loss only)
             output["weight"] = take(weight)[None].detach()
             output["blend_weight"] = take(blend_w)[None, ..., None].detach()
             conf = self.neural_points.points_conf

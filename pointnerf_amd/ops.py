@@ -414,68 +414,61 @@ def gather_rows(src, idx):
     return GatherRows.apply(src, idx)
 
 
+def zero_one_sum(conf_flat, pidx, ray_hit, eps):
+    """The regulariser's forward pass: sum over the neighbor slots of  log(v) + log(1 - v),  v = clamp(gradient_clamp(conf[max(pidx, 0)], 1e-4, 1),
+    eps, 1 - eps), as a scalar tensor (the per-block partial sums, added).  ``ray_hit`` None: every slot of the flat index list ``pidx``
+    (pnerf_zero_one_forward); else ``pidx`` is the DENSE neighbor table [R, ...] of a query and only the rays with ray_hit > 0 count
+    (pnerf_zero_one_forward_rays: no [R'', SR, K] copy of the table is made)."""
+    lib = L.lib()
+    R = 0 if ray_hit is None else int(pidx.shape[0])
+    # the one rule for the number of partial sums: a workgroup per 256 slots of the flat list / per ray of the table, at most 2048
+    part = torch.empty(lib.pnerf_zero_one_blocks(pidx.numel() if ray_hit is None else R * 256), dtype=torch.float32, device=conf_flat.device)
+    if ray_hit is None:
+        L.check(lib.pnerf_zero_one_forward(_ptr(conf_flat), conf_flat.numel(), _ptr(pidx), pidx.numel(), float(eps), _ptr(part), _stream()), "pnerf_zero_one_forward")
+    else:
+        L.check(lib.pnerf_zero_one_forward_rays(_ptr(conf_flat), conf_flat.numel(), _ptr(pidx), _ptr(ray_hit), R, int(pidx.numel() // max(R, 1)), float(eps),
+                                                _ptr(part), _stream()), "pnerf_zero_one_forward_rays")
+    return part.sum()
+
+
+def zero_one_add_grad(conf_flat, pidx, ray_hit, eps, gscale, grad_conf_flat):
+    """The regulariser's backward pass: grad_conf_flat[max(pidx, 0)] += gscale[0] (1 / v - 1 / (1 - v)) where the clamp to [eps, 1 - eps] was
+    inactive (``gscale`` a [1] f32 device tensor; the forms of ``zero_one_sum``)."""
+    if ray_hit is None:
+        L.check(L.lib().pnerf_zero_one_backward(_ptr(conf_flat), conf_flat.numel(), _ptr(pidx), pidx.numel(), float(eps), _ptr(gscale), _ptr(grad_conf_flat),
+                                                _stream()), "pnerf_zero_one_backward")
+    else:
+        R = int(pidx.shape[0])
+        L.check(L.lib().pnerf_zero_one_backward_rays(_ptr(conf_flat), conf_flat.numel(), _ptr(pidx), _ptr(ray_hit), R, int(pidx.numel() // max(R, 1)), float(eps),
+                                                     _ptr(gscale), _ptr(grad_conf_flat), _stream()), "pnerf_zero_one_backward_rays")
+
+
 class ZeroOneConf(torch.autograd.Function):
-    """sum over the neighbor slots of  log(v) + log(1 - v),  v = clamp(gradient_clamp(conf[max(pidx, 0)], 1e-4, 1), eps, 1 - eps): the
-    numerator of the reference's ``loss_zero_one`` on ``conf_coefficient`` (models/base_rendering_model.py:630-641) without materialising
-    the [R'', SR, K] tensor -- one HIP pass forward, one backward (pnerf_zero_one_forward / _backward)."""
-
-    @staticmethod
-    def forward(ctx, conf, pidx, eps):
-        lib = L.lib()
-        c = conf.detach().reshape(-1)
-        _need_cuda(c, "points_conf")
-        idx = pidx.reshape(-1)
-        nb = lib.pnerf_zero_one_blocks(idx.numel())
-        part = torch.empty(nb, dtype=torch.float32, device=c.device)
-        L.check(lib.pnerf_zero_one_forward(_ptr(c), c.numel(), _ptr(idx), idx.numel(), float(eps), _ptr(part), _stream()), "pnerf_zero_one_forward")
-        ctx.save_for_backward(c, idx)
-        ctx.eps, ctx.shape = float(eps), conf.shape
-        return part.sum()
-
-    @staticmethod
-    def backward(ctx, g):
-        c, idx = ctx.saved_tensors
-        grad = torch.zeros_like(c)
-        gs = g.detach().reshape(1).to(torch.float32).contiguous()
-        L.check(L.lib().pnerf_zero_one_backward(_ptr(c), c.numel(), _ptr(idx), idx.numel(), ctx.eps, _ptr(gs), _ptr(grad), _stream()), "pnerf_zero_one_backward")
-        return grad.view(ctx.shape), None, None
-
-
-def zero_one_conf_sum(conf, pidx, eps):
-    return ZeroOneConf.apply(conf, pidx.contiguous(), eps)
-
-
-class ZeroOneConfRays(torch.autograd.Function):
-    """ZeroOneConf over the DENSE neighbor table [R, SR, K] of a query restricted to the rays that hit (ray_hit [R] int32 > 0): the
-    reference's conf_coefficient exists for the hit rays only; this form never copies the table to [R'', SR, K]
-    (pnerf_zero_one_forward_rays / _backward_rays)."""
+    """zero_one_sum / zero_one_add_grad as a differentiable function of points_conf: the numerator of the reference's ``loss_zero_one`` on
+    ``conf_coefficient`` (models/base_rendering_model.py:630-641) without materialising the [R'', SR, K] tensor -- one HIP pass forward, one backward."""
 
     @staticmethod
     def forward(ctx, conf, pidx, ray_hit, eps):
-        lib = L.lib()
         c = conf.detach().reshape(-1)
         _need_cuda(c, "points_conf")
-        R = int(pidx.shape[0])
-        slots = int(pidx.numel() // max(R, 1))
-        nb = lib.pnerf_zero_one_blocks(R * 256)
-        part = torch.empty(nb, dtype=torch.float32, device=c.device)
-        L.check(lib.pnerf_zero_one_forward_rays(_ptr(c), c.numel(), _ptr(pidx), _ptr(ray_hit), R, slots, float(eps), _ptr(part), _stream()), "pnerf_zero_one_forward_rays")
         ctx.save_for_backward(c, pidx, ray_hit)
-        ctx.eps, ctx.shape, ctx.dims = float(eps), conf.shape, (R, slots)
-        return part.sum()
+        ctx.eps, ctx.shape = float(eps), conf.shape
+        return zero_one_sum(c, pidx, ray_hit, eps)
 
     @staticmethod
     def backward(ctx, g):
         c, pidx, ray_hit = ctx.saved_tensors
         grad = torch.zeros_like(c)
-        gs = g.detach().reshape(1).to(torch.float32).contiguous()
-        L.check(L.lib().pnerf_zero_one_backward_rays(_ptr(c), c.numel(), _ptr(pidx), _ptr(ray_hit), ctx.dims[0], ctx.dims[1], ctx.eps, _ptr(gs), _ptr(grad), _stream()),
-                "pnerf_zero_one_backward_rays")
+        zero_one_add_grad(c, pidx, ray_hit, ctx.eps, g.detach().reshape(1).to(torch.float32).contiguous(), grad)
         return grad.view(ctx.shape), None, None, None
 
 
+def zero_one_conf_sum(conf, pidx, eps):
+    return ZeroOneConf.apply(conf, pidx.contiguous().reshape(-1), None, eps)
+
+
 def zero_one_conf_sum_rays(conf, pidx_dense, ray_hit, eps):
-    return ZeroOneConfRays.apply(conf, pidx_dense.contiguous(), ray_hit.contiguous(), eps)
+    return ZeroOneConf.apply(conf, pidx_dense.contiguous(), ray_hit.contiguous(), eps)
 
 
 class ColorLossRays(torch.autograd.Function):

@@ -181,6 +181,26 @@ def test_emulated_fused_zero_one_loss_matches_the_torch_chain():
     assert torch.allclose(b.grad, a.grad, rtol=2e-5, atol=1e-5 * float(a.grad.abs().max()))
 
 
+def _zero_one_bars(value, ref, grad, ref_grad):
+    """the bars of test_emulated_fused_zero_one_loss_matches_the_torch_chain"""
+    assert abs(float(value) - float(ref)) <= 2e-5 * abs(float(ref))
+    assert torch.allclose(grad, ref_grad, rtol=2e-5, atol=1e-5 * float(ref_grad.abs().max()))
+
+
+@pytest.mark.parametrize("shape", ["flat_6000", "rays_37x192", "rays_5x300"])
+def test_emulated_unified_zero_one_pass_matches_the_torch_chain(shape):
+    """the one forward / one backward kernel of the zero-one regulariser in both forms (tests/zero_one_case.py), value and conf gradient with a
+    scale factor on the output; the rays forms also against the flat form on the compacted table of the hit rays"""
+    import zero_one_case
+    zero_one_case.check_against_the_chain(shape, "cpu", _zero_one_bars)
+
+
+def test_emulated_unified_zero_one_pass_exact_conditions():
+    """no tolerance: rays form == flat form where both map threads to elements identically; all rays missed and an empty list give 0 and no gradient"""
+    import zero_one_case
+    zero_one_case.check_exact_conditions("cpu")
+
+
 def test_emulated_two_plane_weight_gradients():
     """pnerf_set_wgrad_planes(2): the saved operands' residual planes, the three-product weight-gradient launches and the whole-X0 path of the
     fused step, on the emulator: same bars as the default mode, and the MLP gradients of the two modes agree to the one-plane rounding."""

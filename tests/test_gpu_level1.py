@@ -278,3 +278,23 @@ def test_fused_zero_one_loss_matches_the_torch_chain():
     assert abs(float(got) - float(ref)) <= 1e-5 * abs(float(ref))
     scale = float(a.grad.abs().max())
     assert float((b.grad - a.grad).abs().max()) <= 1e-4 * scale      # point 0 collects ~1e7 terms on both sides: fp32 summation order
+
+
+def _zero_one_bars(value, ref, grad, ref_grad):
+    """the bars of test_fused_zero_one_loss_matches_the_torch_chain"""
+    assert abs(float(value) - float(ref)) <= 1e-5 * abs(float(ref))
+    assert float((grad - ref_grad).abs().max()) <= 1e-4 * float(ref_grad.abs().max())
+
+
+@pytest.mark.parametrize("shape", ["flat_6000", "rays_37x192", "rays_5x300"])
+def test_unified_zero_one_pass_matches_the_torch_chain(shape):
+    """the one forward / one backward kernel of the zero-one regulariser in both forms at the smallest shapes that reach each of its loop paths
+    (tests/zero_one_case.py); the rays forms also against the flat form on the compacted table of the hit rays"""
+    import zero_one_case
+    zero_one_case.check_against_the_chain(shape, "cuda:0", _zero_one_bars)
+
+
+def test_unified_zero_one_pass_exact_conditions():
+    """no tolerance: rays form == flat form where both map threads to elements identically; all rays missed and an empty list give 0 and no gradient"""
+    import zero_one_case
+    zero_one_case.check_exact_conditions("cuda:0")

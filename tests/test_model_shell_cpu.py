@@ -387,3 +387,74 @@ def test_compute_losses_on_the_fused_colour_form_equals_the_compacted_form(tmp_p
     for k in la:
         assert abs(la[k] - lb[k]) <= 1e-6 * max(1.0, abs(la[k])), (k, la[k], lb[k])
     assert torch.allclose(ga, gb, rtol=1e-6, atol=1e-9) and float(gb[~hit].abs().max()) == 0.0 and float(gb[hit].abs().max()) > 0.0
+
+
+def test_hot_path_loss_and_compute_losses_agree_on_every_output_form(tmp_path, monkeypatch):
+    """The two callers of pointnerf_amd/losses.py on the same seeded renderer results, handed over in each of the three zero-one forms
+    (`_zero_one_sum`, `_zero_one`, the `conf_coefficient` tensor) x both colour forms (`_dense_color`, compacted): for each dict
+    dist.hot_path_loss and MvsPointsVolumetricModel.compute_losses give the same total and the same gradients on the ray colours and on
+    points_conf (the lego items: ray_masked 1.0, ray_miss 0.0, full image 0.0, zero-one on conf_coefficient).  The shell adds the reference's
+    1e-6 once per colour ITEM, hot_path_loss once: three items, so its total is 2e-6 above.  The fused passes are replaced by their torch
+    statements, as in the test above."""
+    from pointnerf_amd import dist as pdist, ops
+    from pointnerf_amd.neural_points_volumetric_model import gradient_clamp
+
+    def zero_one_rays(conf, pidx_dense, ray_hit, eps):
+        v = gradient_clamp(conf.reshape(-1)[pidx_dense[ray_hit > 0].long().clamp(min=0)]).clamp(eps, 1 - eps)
+        return (torch.log(v) + torch.log(1 - v)).sum()
+
+    monkeypatch.setattr(ops, "color_loss_sum_rays", lambda color, gt, ray_hit: (((color - gt) ** 2) * (ray_hit > 0)[:, None]).sum())
+    monkeypatch.setattr(ops, "zero_one_conf_sum_rays", zero_one_rays)
+    g = torch.Generator().manual_seed(9)
+    R, SR, K, N = 41, 8, 4, 60
+    hit = torch.rand(R, generator=g) < 0.55
+    idx, ray_hit = torch.nonzero(hit).squeeze(1), hit.to(torch.int32)
+    gt, bg = torch.rand(1, R, 3, generator=g), torch.ones(1, 3)
+    opacity, bg_trans = torch.rand(R, SR, generator=g), torch.rand(R, generator=g)
+    pidx = torch.randint(-1, N, (R, SR, K), generator=g, dtype=torch.int32)
+    color0, conf0 = torch.rand(R, 3, generator=g), torch.rand(1, N, 1, generator=g) * 1.2 - 0.1
+    opt = config.lego_train_opt(gpu_ids=[], checkpoints_dir=str(tmp_path), name="run", num_point=0, K=K, SR=SR)
+    assert list(zip(opt.color_loss_items, opt.color_loss_weights)) == [("ray_masked_coarse_raycolor", 1.0), ("ray_miss_coarse_raycolor", 0.0), ("coarse_raycolor", 0.0)]
+    assert opt.zero_one_loss_items == ["conf_coefficient"]
+    count = int(hit.sum()) * SR * K
+
+    def renderer_output(color_form, zo_form):
+        color, conf = color0.clone().requires_grad_(True), conf0.clone().requires_grad_(True)
+        if color_form == "dense":
+            raw = dict(ray_mask=hit.to(torch.int8)[None], _dense_color=(color, ray_hit, int(hit.sum())), _dense_aux=(opacity, bg_trans))
+        else:
+            raw = dict(ray_mask=hit.to(torch.int8)[None], _hit_index=idx, coarse_raycolor=color[idx][None], coarse_point_opacity=opacity[idx][None],
+                       coarse_is_background=bg_trans[idx][None, :, None], queried_shading=torch.zeros(1, idx.numel(), 3))
+        if zo_form == "sum":
+            raw["_zero_one_sum"] = (zero_one_rays(conf, pidx, ray_hit, opt.zero_epsilon), count)
+        elif zo_form == "pass":
+            raw["_zero_one"] = (conf, pidx, ray_hit, count)
+        else:
+            raw["conf_coefficient"] = gradient_clamp(conf.reshape(-1)[pidx[idx].long().clamp(min=0)])[None]
+        return raw, color, conf
+
+    res = {}
+    for color_form in ("compacted", "dense"):
+        for zo_form in ("sum", "pass", "tensor"):
+            raw, color, conf = renderer_output(color_form, zo_form)
+            hot = pdist.hot_path_loss(opt, raw, gt, opt.zero_epsilon)
+            hot.backward()
+            raw2, color2, conf2 = renderer_output(color_form, zo_form)
+            m = create_model(opt)
+            m.set_input(dict(gt_image=gt, bg_color=bg))
+            m._raw, m.output = raw2, fill_invalid(raw2, bg)
+            m.compute_losses()
+            m.loss_total.backward()
+            shell = float(m.loss_total) - 2e-6
+            assert abs(float(hot) - shell) <= 1e-6 * max(1.0, abs(shell)), (color_form, zo_form, float(hot), shell)
+            assert torch.allclose(color.grad, color2.grad, rtol=1e-6, atol=1e-9) and float(color.grad[hit].abs().max()) > 0.0, (color_form, zo_form)
+            assert torch.allclose(conf.grad, conf2.grad, rtol=1e-6, atol=1e-9) and float(conf.grad.abs().max()) > 0.0, (color_form, zo_form)
+            assert set(m.get_current_losses()) == {"total", "ray_masked_coarse_raycolor", "ray_miss_coarse_raycolor", "coarse_raycolor", "conf_coefficient"}
+            res[color_form, zo_form] = (float(hot), color.grad, conf.grad)
+    # ...and the six forms carry the same loss: totals to the same bar; the gradients to fp32 accumulation order (the tensor form sums a
+    # point's terms through the gather's backward, the others through one index: a few hundred terms of rounding 6e-8 each)
+    l0, gc0, gf0 = res["compacted", "tensor"]
+    for key, (l, gc, gf) in res.items():
+        assert abs(l - l0) <= 1e-6 * max(1.0, abs(l0)), key
+        assert torch.allclose(gc, gc0, rtol=1e-6, atol=1e-9), key
+        assert float((gf - gf0).abs().max()) <= 1e-5 * float(gf0.abs().max()), key
