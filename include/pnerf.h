@@ -363,6 +363,33 @@ size_t pnerf_image_metrics_workspace_bytes(int H, int W, int win);     /* run/ev
 int pnerf_image_metrics(const float *d_img, const float *d_gt, int H, int W, int win, double data_range, int quantize8, double *d_out4,
                         void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- the probe pass of the point-growing step (run/train_ft.py:417-530 probe_hole) on the renderer's dense results.
+ *
+ * pnerf_probe_rays: the `opt.prob == 1` outputs of NeuralPointsRayMarching.forward (models/neural_points_volumetric_model.py:331-352) for
+ * all R submitted rays from the DENSE tensors of pnerf_query / pnerf_render_forward (d_opacity [R,SR], d_weight [R,SR,K], d_sample_loc
+ * [R,SR,3], d_sample_pidx [R,SR,K], d_ray_hit [R]); no [R'',SR,K] copy is read or written.  For a ray with d_ray_hit[r] > 0, with s* the
+ * LOWEST sample index among the maxima of d_opacity[r, 0 .. SR-1] and p_k = max(d_sample_pidx[r, s*, k], 0) (an empty slot reads point 0,
+ * models/neural_points/neural_points.py:708), w_k = d_weight[r, s*, k] * min(max(conf[p_k], 1e-4), 1)
+ * (gradient_clamp, models/aggregators/point_aggregators.py:722-724):
+ *   d_max_opacity [R]    ray_max_shading_opacity = d_opacity[r, s*]        d_loc3 [R,3]   ray_max_sample_loc_w = d_sample_loc[r, s*, :]
+ *   d_far_dist    [R]    ray_max_far_dist = min_k |xyz[p_k] - loc| over ALL K slots (point 0 of the empty ones included, as in the reference)
+ *   d_avg_color3 [R,3], d_avg_dir3 [R,3], d_avg_conf [R], d_avg_emb32 [R,32]    shading_avg_* = sum_k w_k row_k, fp32
+ * A ray with d_ray_hit[r] <= 0 gets zeros in all seven (fill_invalid's zero fill, :121-122); its input rows are not read.
+ * PNERF_E_INVAL: K outside 1..PNERF_MAX_K, SR <= 0, R < 0, a null pointer; PNERF_E_UNSUP: pts->feat_dim != 32.  R == 0: nothing is enqueued. */
+int pnerf_probe_rays(const pnerf_points *pts, const float *d_opacity, const float *d_weight, const float *d_sample_loc,
+                     const int32_t *d_sample_pidx, const int32_t *d_ray_hit, int R, int SR, int K, float *d_max_opacity, float *d_loc3,
+                     float *d_far_dist, float *d_avg_color3, float *d_avg_dir3, float *d_avg_conf, float *d_avg_emb32, void *stream);
+/* pnerf_probe_hole_mask: the candidate rule of probe_hole per pixel of an [H,W] view (run/train_ft.py:489-500 with bloat_inds :532-540):
+ *   hit = d_ray_mask > 0;  miss = !hit && |d_gt - bg| > 0.002 && d_edge;  near = any miss in the 3 x 3 neighborhood clamped to the image;
+ *   far_thresh > 0: near |= hit && d_far_dist > far_thresh && |d_gt - d_raycolor| < 0.1;   d_flags = hit && near && d_max_opacity > opacity_thresh
+ * d_ray_mask [H,W] i8, d_max_opacity / d_far_dist [H,W] f32, d_raycolor / d_gt [H,W,3] f32, d_edge [H,W] u8 (pixels the view has rays
+ * for), bg3_host: 3 floats on the host, d_flags [H,W] i32 0/1 -- the input of pnerf_compact_valid, which turns it into the ascending
+ * row-major candidate list with its count on the device.  The norms are sqrtf of the fp32 sum of squares.  PNERF_E_INVAL: H or W <= 0,
+ * a null pointer. */
+int pnerf_probe_hole_mask(const int8_t *d_ray_mask, const float *d_max_opacity, const float *d_far_dist, const float *d_raycolor,
+                          const float *d_gt, const uint8_t *d_edge, const float *bg3_host, int H, int W, float opacity_thresh,
+                          float far_thresh, int32_t *d_flags, void *stream);
+
 /* ---- diagnostics: ONE v_mfma_f32_32x32x16_f16, D = A B with caller-built fragments: d_a / d_b [64 lanes][8] f16 (lane l holds
  * A[l & 31][8 (l >> 5) .. + 7] resp. B[8 (l >> 5) .. + 7][l & 31]), d_out [64 lanes][16] f32 (register r of lane l =
  * D[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31]).  The tests pin with it the fragment layout and the un-flushed handling of f16

@@ -119,6 +119,10 @@ PROTOTYPES = {
                                         c_void_p, c_void_p, c_void_p]),
     "pnerf_image_metrics_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pnerf_image_metrics": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnerf_probe_rays": (c_int, [ctypes.POINTER(Points), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pnerf_probe_hole_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_f32), c_int, c_int,
+                                      c_f32, c_f32, c_void_p, c_void_p]),
     "pnerf_debug_mfma_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mix_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mfma_rate": (c_int, [c_int, c_int, c_void_p, ctypes.POINTER(ctypes.c_double), c_void_p]),

@@ -11,6 +11,8 @@ boolean row-gather at the very end (the only host sync besides reading the valid
 ``opt.prob==1`` adds the probe outputs of :331-362 (per-ray argmax-opacity sample, its location, nearest-neighbor
 distance and weighted average colour/dir/conf/embedding) used by ``probe_hole`` (run/train_ft.py:417-530): they touch
 one sample per ray, so they are small gathers on top of the dense render (``pnerf_gather_rows`` for the point rows).
+A caller that sets ``fused_probe`` (probe.probe_hole(fused=True)) gets them for all R rays from one ``pnerf_probe_rays`` launch instead
+(``_output_forms``).
 """
 import os
 
@@ -131,7 +133,7 @@ class NeuralPointsRayMarching(nn.Module):
 
     def _output_forms(self):
         """THE decision of one ``forward`` call, from the caller's flags and the options: (dense colours handed out?, form of the zero-one
-        regulariser on conf_coefficient).
+        regulariser on conf_coefficient, probe outputs from the fused pass?).
 
         ``fused_zero_one`` / ``fused_color_loss`` (ours; set by callers whose loss goes through dist.hot_path_loss, and by the model shell of this
         package -- fused_color_loss when every colour-loss item with a non-zero weight is a ray_masked / ray_miss one, the lego script's setting:
@@ -143,22 +145,28 @@ class NeuralPointsRayMarching(nn.Module):
         loss, the probe outputs, a caller without the flag); None -- nobody reads them.
         Dense colours: a TRAINING step gets the dense ray colours and the hit flags under "_dense_color" (ops.ColorLossRays: one pass forward, one
         backward, d colour written for every ray) and the compacted [1, R'', ...] outputs are not formed -- no argsort, no index_selects, no
-        scatter-back in the backward (~25 launches per step)."""
+        scatter-back in the backward (~25 launches per step).
+        ``fused_probe`` (ours; set by probe.probe_hole(fused=True) for the duration of its call) says that the only consumer of an ``opt.prob == 1``
+        forward is the probe pass: under no_grad the third element is True and the forward hands out the dense colour form plus "_dense_probe", the
+        seven probe outputs for all R rays from ONE ops.probe_rays launch -- no argsort / index_select route, no weight / blend_weight /
+        conf_coefficient [1, R'', SR, K] copies, no boolean-mask index; fill_invalid(prob=1) only adds the batch axis."""
         opt, grad = self.opt, torch.is_grad_enabled()
+        if bool(getattr(self, "fused_probe", False)) and getattr(opt, "prob", 0) == 1 and not grad:
+            return True, None, True
         loss_only = bool(getattr(self, "fused_zero_one", False)) and opt.sparse_loss_weight <= 0 and getattr(opt, "prob", 0) == 0
         has_item = "conf_coefficient" in getattr(opt, "zero_one_loss_items", ())
         if has_item and loss_only:
             zero_one = "render" if grad else "pass"
         else:
             zero_one = "tensor" if (has_item or opt.sparse_loss_weight > 0 or getattr(opt, "prob", 0) != 0) else None
-        return bool(getattr(self, "fused_color_loss", False)) and grad and loss_only, zero_one
+        return bool(getattr(self, "fused_color_loss", False)) and grad and loss_only, zero_one, False
 
     def forward(self, campos, raydir, gt_image=None, bg_color=None, camrotc2w=None, pixel_idx=None, near=None, far=None,
                 focal=None, h=None, w=None, intrinsic=None, **kargs):
         opt = self.opt
         if "bg_ray" in kargs:
             bg_color = None
-        dense_color, zero_one = self._output_forms()
+        dense_color, zero_one, fused_probe = self._output_forms()
         ray_color, opacity, bg_trans, blend_w, decoded, weight, zo_sum, dense = self.render_dense(
             campos, raydir, camrotc2w, near, far, bg_color, zero_one_eps=getattr(opt, "zero_epsilon", 1e-3) if zero_one == "render" else None)
         hit = dense["ray_hit"] > 0
@@ -192,7 +200,14 @@ class NeuralPointsRayMarching(nn.Module):
             conf = self.neural_points.points_conf
             pidx_hit = take(dense["sample_pidx"])
             output["conf_coefficient"] = gradient_clamp(ops.gather_rows(conf.reshape(-1, 1), pidx_hit)[..., 0])[None]
-        if getattr(opt, "prob", 0) == 1 and output["coarse_point_opacity"].shape[1] > 0:
+        if fused_probe:
+            if n_hit > 0:                         # (a batch that hit nothing carries no probe outputs, like the compacted form below)
+                npnt = self.neural_points
+                rows = lambda t: t.detach().reshape(-1, t.shape[-1]).contiguous()
+                pts = ops.make_points(rows(npnt.xyz), rows(npnt.points_embeding), rows(npnt.points_conf), rows(npnt.points_dir), rows(npnt.points_color))
+                output["_dense_probe"] = ops.probe_rays(pts, opacity.detach(), weight.detach(), dense["sample_loc"], dense["sample_pidx"], dense["ray_hit"],
+                                                        hit.shape[0], SR, K)
+        elif getattr(opt, "prob", 0) == 1 and output["coarse_point_opacity"].shape[1] > 0:
             self._probe_outputs(output, dense, hit)
         return output
 
@@ -249,6 +264,10 @@ def fill_invalid(output, bg_color, tonemap_func=None, bg_ray=None, prob=0):
         qs = torch.where(hitb[:, None], torch.zeros((), dtype=torch.float32, device=dev), torch.ones([OR, 3], dtype=torch.float32, device=dev))[None]
         out = dict(output)
         out.update(coarse_is_background=bgt, coarse_mask=1 - bgt, coarse_raycolor=col, coarse_point_opacity=op, queried_shading=qs)
+        if prob == 1 and "_dense_probe" in output:
+            # the fused probe form: ops.probe_rays has written every ray's row already, zeros for the misses (:121-122 "unmask")
+            for k in PROBE_KEYS:
+                out[k] = output["_dense_probe"][k][None]
         return out
     sel = output["_hit_index"] if "_hit_index" in output else ray_mask[0] > 0      # index tensor: no nonzero() synchronisation
     dev = output["coarse_raycolor"].device

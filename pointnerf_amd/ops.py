@@ -580,6 +580,51 @@ def image_metrics(img, gt, win=11, data_range=2.0, quantize8=True):
     return torch.stack([out4[0] / float(H * W * 3), out4[1:].sum() / float(3 * n_win)])
 
 
+# ------------------------------------------------------------------------------------------ probe pass
+PROBE_RAY_KEYS = (("ray_max_shading_opacity", 1), ("ray_max_sample_loc_w", 3), ("ray_max_far_dist", 1), ("shading_avg_color", 3),
+                  ("shading_avg_dir", 3), ("shading_avg_conf", 1), ("shading_avg_embedding", 32))
+
+
+def _dense_arg(t, name, dtype, numel):
+    _need_cuda(t, name)
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError("pointnerf_amd: %s must be a contiguous %s tensor of %d elements, got %s %s" % (name, dtype, numel, t.dtype, list(t.shape)))
+    return t
+
+
+def probe_rays(pts, opacity, weight, sample_loc, sample_pidx, ray_hit, R, SR, K):
+    """pnerf_probe_rays: the ``opt.prob == 1`` outputs of the reference's ray marcher (neural_points_volumetric_model.py:331-352) for ALL R
+    submitted rays from the renderer's dense tensors (opacity [R,SR], weight [R,SR,K], sample_loc [R,SR,3], sample_pidx [R,SR,K] i32, ray_hit [R]
+    i32; ``pts`` = make_points(...) of the cloud), one launch, no host read.  Returns the seven tensors under the reference's key names, [R, C]
+    each (C = 1, 3, 1, 3, 3, 1, 32 in the order of PROBE_RAY_KEYS); the rows of the rays that missed are zero."""
+    R, SR, K = int(R), int(SR), int(K)
+    f32, i32 = torch.float32, torch.int32
+    _dense_arg(opacity, "opacity", f32, R * SR); _dense_arg(weight, "weight", f32, R * SR * K); _dense_arg(sample_loc, "sample_loc", f32, R * SR * 3)
+    _dense_arg(sample_pidx, "sample_pidx", i32, R * SR * K); _dense_arg(ray_hit, "ray_hit", i32, R)
+    out = {k: torch.empty(R, c, dtype=f32, device=opacity.device) for k, c in PROBE_RAY_KEYS}
+    L.check(L.lib().pnerf_probe_rays(ctypes.byref(pts), _ptr(opacity), _ptr(weight), _ptr(sample_loc), _ptr(sample_pidx), _ptr(ray_hit), R, SR, K,
+                                     *[_ptr(out[k]) for k, _ in PROBE_RAY_KEYS], _stream()), "pnerf_probe_rays")
+    return out
+
+
+def probe_hole_flags(ray_mask, max_opacity, far_dist, raycolor, gt, edge, bg, opacity_thresh, far_thresh=-1.0):
+    """pnerf_probe_hole_mask: the candidate rule of probe_hole (run/train_ft.py:489-500) on the maps of one [H, W] view -> int32 0/1 flags
+    [H, W] (``compact_valid`` turns them into the ascending candidate list).  ray_mask [H,W(,1)] int8, max_opacity / far_dist [H,W(,1)] f32,
+    raycolor / gt [H,W,3] f32, edge [H,W] bool, bg: three numbers (read on the host)."""
+    H, W = int(edge.shape[0]), int(edge.shape[1])
+    n = H * W
+    _need_cuda(edge, "edge")
+    if edge.dtype != torch.bool or not edge.is_contiguous() or edge.dim() != 2:
+        raise ValueError("pointnerf_amd: edge must be a contiguous [H, W] bool tensor")
+    _dense_arg(ray_mask, "ray_mask", torch.int8, n); _dense_arg(max_opacity, "max_opacity", torch.float32, n); _dense_arg(far_dist, "far_dist", torch.float32, n)
+    _dense_arg(raycolor, "raycolor", torch.float32, n * 3); _dense_arg(gt, "gt", torch.float32, n * 3)
+    bg3 = (ctypes.c_float * 3)(*[float(x) for x in np.asarray(host_array(bg), dtype=np.float64).reshape(-1)[:3]])
+    flags = torch.empty(H, W, dtype=torch.int32, device=edge.device)
+    L.check(L.lib().pnerf_probe_hole_mask(_ptr(ray_mask), _ptr(max_opacity), _ptr(far_dist), _ptr(raycolor), _ptr(gt), _ptr(edge.view(torch.uint8)), bg3,
+                                          H, W, float(opacity_thresh), float(far_thresh), _ptr(flags), _stream()), "pnerf_probe_hole_mask")
+    return flags
+
+
 # ------------------------------------------------------------------------------------------ profiling
 def mfma_rate_tflops(mode=2, ms_target=60.0, device=None):
     """TFLOP/s of register-resident v_mfma_f32_32x32x16_f16 on the whole chip (pnerf_debug_mfma_rate; mode 0 zero operands, 1 one constant,

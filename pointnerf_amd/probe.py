@@ -13,12 +13,22 @@ Same selection rule, same outputs (add_xyz, add_embedding, add_color, add_dir, a
 One quirk of the reference is reproduced on purpose because it changes the result: ``add_conf`` is multiplied by
 ``opt.prob_mul`` once per processed view AFTER concatenation (train_ft.py:505), so candidates found in earlier views are
 scaled again by every later view.
+
+``probe_hole(..., fused=True)`` (what ``prune_and_grow_step``, this package's own caller, passes) runs the same step without the reference's
+compacted shapes: the ray marcher hands out the seven probe outputs for all submitted rays from one ``pnerf_probe_rays`` launch
+(``fused_probe``, neural_points_volumetric_model.py), the candidate rule is one ``pnerf_probe_hole_mask`` launch whose flags
+``pnerf_compact_valid`` turns into the ascending candidate list, and the five ``add_*`` blocks are row gathers by that list.  The host
+reads one number per view, the candidate count (besides the render's own read of its counters per chunk); the unfused form synchronises
+twice more per chunk with a hit (``nonzero`` behind two boolean-mask indexes) and six times more per view.  Same candidates in the same
+order (DESIGN.md 4.4 has the measured times).
 """
 import random
 
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from . import ops
 
 PROBE_MAP_KEYS = ("coarse_raycolor", "ray_mask", "ray_max_sample_loc_w", "ray_max_far_dist", "ray_max_shading_opacity",
                   "shading_avg_color", "shading_avg_dir", "shading_avg_conf", "shading_avg_embedding")
@@ -96,8 +106,26 @@ def render_probe_maps(model, view, height, width, chunk=160000):
 
 
 @torch.no_grad()
-def probe_hole(model, views, opt, height, width, test_steps=0, opacity_thresh=0.7, frame_ids=None, chunk=160000, on_view=None):
+def fused_candidates(maps, pixel_idx, gt_rays, bg, height, width, opacity_thresh, far_thresh):
+    """The candidates of one view without a boolean-mask index: (ascending row-major pixel indices [n] int64, flags [H,W] int32).  Same
+    rule and same inputs as ``hole_mask`` on the view's ``edge`` / ``gt`` maps; ONE host read, the count."""
+    dev = pixel_idx.device
+    edge = torch.zeros([height, width], dtype=torch.bool, device=dev)
+    pl = pixel_idx[0].to(torch.long)
+    edge[pl[:, 1], pl[:, 0]] = True
+    # gt[edge] = gt_rays: the i-th ray's colour goes to the i-th pixel of the view in row-major order -- by rank, no nonzero()
+    rank = (torch.cumsum(edge.reshape(-1).to(torch.int64), 0) - 1).clamp_(min=0)
+    gt = torch.where(edge.reshape(-1, 1), gt_rays.reshape(-1, 3).to(torch.float32).index_select(0, rank), torch.zeros((), dtype=torch.float32, device=dev))
+    flags = ops.probe_hole_flags(maps["ray_mask"], maps["ray_max_shading_opacity"], maps["ray_max_far_dist"], maps["coarse_raycolor"],
+                                 gt.reshape(height, width, 3), edge, bg, opacity_thresh, far_thresh)
+    cand, counters = ops.compact_valid(flags.reshape(-1))
+    return cand[:int(counters[0])].to(torch.long), flags
+
+
+@torch.no_grad()
+def probe_hole(model, views, opt, height, width, test_steps=0, opacity_thresh=0.7, frame_ids=None, chunk=160000, on_view=None, fused=False):
     """Returns (add_xyz [M,3], add_embedding [M,F], add_color [M,3], add_dir [M,3], add_conf [M,1]) on the device.
+    ``fused``: the probe outputs and the candidate mask from the HIP probe kernels (module docstring); same result.
 
     ``views``: a sequence (or anything with ``__getitem__``/``__len__``) of the datasets' per-view dicts in ``no_crop`` form:
     raydir [1,P,3], pixel_idx [1,h,w,2] or [1,P,2] (px, py), gt_image [1,P,3], bg_color [1,3], campos, camrotc2w, near, far,
@@ -112,6 +140,10 @@ def probe_hole(model, views, opt, height, width, test_steps=0, opacity_thresh=0.
         model.opt.query_size = np.asarray(opt.prob_kernel_size[tier * 3:tier * 3 + 3])
     model.opt.prob = 1
     model.opt.no_loss = 1
+    marcher = model.net_ray_marching if fused else None
+    if fused:
+        saved["fused_probe"] = getattr(marcher, "fused_probe", False)
+        marcher.fused_probe = True
     if frame_ids is None:
         frame_ids, _ = select_probe_frames(model, len(views), opt)
     try:
@@ -120,6 +152,19 @@ def probe_hole(model, views, opt, height, width, test_steps=0, opacity_thresh=0.
             bg = view["bg_color"].to(dev).reshape(1, 3)
             maps, pixel_idx = render_probe_maps(model, view, height, width, chunk)
             if "ray_max_shading_opacity" not in maps:         # no ray of this view hit anything
+                continue
+            if fused:
+                # (bg: the view's own tensor, whose host copy the render has cached already -- ops.host_array -- not the reshaped one above)
+                cand, flags = fused_candidates(maps, pixel_idx, view["gt_image"].to(dev), view["bg_color"], height, width, opacity_thresh,
+                                               getattr(opt, "far_thresh", -1.0))
+                rows = lambda key: maps[key].reshape(height * width, -1).index_select(0, cand)
+                add["xyz"] = torch.cat([add["xyz"], rows("ray_max_sample_loc_w")], dim=0)
+                add["conf"] = torch.cat([add["conf"], rows("shading_avg_conf")], dim=0) * opt.prob_mul
+                add["color"] = torch.cat([add["color"], rows("shading_avg_color")], dim=0)
+                add["dir"] = torch.cat([add["dir"], rows("shading_avg_dir")], dim=0)
+                add["emb"] = torch.cat([add["emb"], rows("shading_avg_embedding")], dim=0)
+                if on_view is not None:
+                    on_view(i, maps, flags > 0)
                 continue
             edge = torch.zeros([height, width], dtype=torch.bool, device=dev)
             pl = pixel_idx[0].to(torch.long)
@@ -136,6 +181,8 @@ def probe_hole(model, views, opt, height, width, test_steps=0, opacity_thresh=0.
                 on_view(i, maps, m)
     finally:
         model.opt.query_size, model.opt.prob, model.opt.no_loss = saved["query_size"], saved["prob"], saved["no_loss"]
+        if fused:
+            marcher.fused_probe = saved["fused_probe"]
     if opt.prob_mode == 0 and opt.prob_num_step > 1 and hasattr(model, "num_probe"):
         model.reset_ray_miss_ranking()
     return add["xyz"], add["emb"], add["color"], add["dir"], add["conf"]
@@ -164,7 +211,7 @@ def prune_and_grow_step(model, views, opt, total_steps, height, width, real_star
             model.eval()
             try:
                 xyz, emb, color, dirs, conf = probe_hole(model, views, opt, height, width, test_steps=total_steps,
-                                                         opacity_thresh=opt.prob_thresh)
+                                                         opacity_thresh=opt.prob_thresh, fused=True)
             finally:
                 model.opt.is_train = is_train
                 model.train()
