@@ -152,7 +152,9 @@ int pnerf_mlp_pack(const float *d_params, void *d_packed, void *stream);
 typedef struct pnerf_camera {
     float campos[3];
     float camrot[9];       /* c2w rotation, row-major */
-    float rw2c[9];         /* NeuralPoints.Rw2c, row-major (identity unless normview) */
+    float rw2c[9];         /* NeuralPoints.Rw2c when it is ONE [3,3] frame, row-major (identity in every training script): rotates the first
+                            * three distance components, the points' stored directions and the view direction (v -> rw2c v).  A cloud
+                            * with one frame PER POINT (scene editing) passes pnerf_points.frames instead; rw2c is then not read */
     float vsize_z;         /* unscaled opt.vsize[2] (ray-dist clamp) */
     int32_t raydist_mode_unit;
     float bg[3];           /* background colour */
@@ -166,6 +168,14 @@ typedef struct pnerf_points {        /* the neural point cloud, all [N,*] row-ma
     const float *dir;                /* [N,3]  */
     const float *color;              /* [N,3]  */
     int32_t n, feat_dim;
+    const float *frames;             /* optional [N,9] (NULL: cam.rw2c for every point): NeuralPoints.Rw2c [N,3,3] of a composed scene
+                                      * (run/editing.py; models/aggregators/point_aggregators.py:492-496,506,526,566), row-major as in the
+                                      * checkpoint.  A neighbor row of point p uses F[p] for its distance components and stored direction;
+                                      * the view direction of a sample uses the frame of the sample's slot-0 point (empty: point 0) -- also in
+                                      * the rows' (dir - view, dir . view) extras.  RENDER-ONLY: with d_saved != NULL (a training forward) or in
+                                      * pnerf_render_backward / pnerf_agg_backward -> PNERF_E_INVAL; served by the default inference arithmetic
+                                      * only: pnerf_set_inference_products(2) or bit 0 of pnerf_set_cross_terms_where -> PNERF_E_UNSUP.
+                                      * pnerf_agg_forward: indexed like the other pseudo-point arrays, by the slot number */
 } pnerf_points;
 
 typedef struct pnerf_point_grads {   /* gradient accumulators (added to, never zeroed) */

@@ -36,7 +36,7 @@ class Camera(ctypes.Structure):
 
 class Points(ctypes.Structure):
     _fields_ = [("xyz", c_void_p), ("embedding", c_void_p), ("conf", c_void_p), ("dir", c_void_p),
-                ("color", c_void_p), ("n", ctypes.c_int32), ("feat_dim", ctypes.c_int32)]
+                ("color", c_void_p), ("n", ctypes.c_int32), ("feat_dim", ctypes.c_int32), ("frames", c_void_p)]
 
 
 class AdamTensor(ctypes.Structure):

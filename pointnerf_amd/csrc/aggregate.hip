@@ -391,6 +391,10 @@ struct FwdArgs {
     float *decoded, *weight;
     PnSaved sv;                 // fs always valid; the rest only when TRAIN
 };
+// the argument of the FRAMES instances (per-point Rw2c frames, pnerf_points.frames [N,9]); every other instance keeps FwdArgs as it is
+struct FwdArgsF : FwdArgs { const float *frames; };
+template <bool FRAMES> struct FwdArgsOf { using type = FwdArgs; };
+template <> struct FwdArgsOf<true> { using type = FwdArgsF; };
 
 __device__ __forceinline__ void rot3(const float *M /*row-major*/, float x, float y, float z, bool transpose, float &ox, float &oy, float &oz) {
     // transpose=false: out_j = sum_i v_i M[i][j] (v @ M);  true: out_j = sum_i v_i M[j][i] (v @ M^T)
@@ -512,7 +516,8 @@ struct FGather {               // what a thread holds of one tile row (4 threads
     float4 e0, e1;             // its 8 embedding dims
     float px, py, pz, lx, ly, lz, cf;
     float ppx, ppy, ppz, lpx, lpy, lpz;   // optional caller-supplied perspective coordinates
-    float dxv, dyv, dzv, cx, cy, cz, rx, ry, rz;   // q == 0 only
+    float dxv, dyv, dzv, cx, cy, cz, rx, ry, rz;   // q == 0 only (FRAMES: direction and ray of every thread of the row)
+    float fx, fy, fz, gx, gy, gz;                  // FRAMES only: row min(q, 2) of the frame of the row's point / of the sample's slot-0 point
 };
 
 // sample id of row `row` of tile `tile` (or -1)
@@ -522,8 +527,8 @@ __device__ __forceinline__ int f_sample_of(const FwdArgs &a, long long tile, int
     return (ls < a.TS && vs < Ns) ? a.valid_list[vs] : -1;
 }
 
-template <bool PERS>
-__device__ __forceinline__ void f_gather(const FwdArgs &a, FGather &G, int si_, int p_, int q) {
+template <bool PERS, bool FRAMES = false>
+__device__ __forceinline__ void f_gather(const FwdArgs &a, FGather &G, int si_, int p_, int q, const float *frames = nullptr) {
     const int p = p_ > 0 ? p_ : 0, si = si_ > 0 ? si_ : 0;     // empty slots / rows read point 0 / sample 0 like the reference (neural_points.py:709); their weight is 0
     const float *ep = a.emb + (long long)p * PN_F + EPT * q;
     G.e0 = *reinterpret_cast<const float4 *>(ep); G.e1 = *reinterpret_cast<const float4 *>(ep + 4);
@@ -534,7 +539,19 @@ __device__ __forceinline__ void f_gather(const FwdArgs &a, FGather &G, int si_, 
         G.lpx = a.loc_pers[(long long)si * 3]; G.lpy = a.loc_pers[(long long)si * 3 + 1]; G.lpz = a.loc_pers[(long long)si * 3 + 2];
     }
     G.cf = a.conf[p];
-    if (q == 0) {
+    if (FRAMES) {
+        // per-point frames: thread q of the row (q < 3) forms component q of F[p] (xyz - loc), of F[p] dir and of F[slot 0] raydir, so it holds
+        // ROW q of the two frames (3 + 3 floats, not 9 + 9) and the row's direction and ray; thread 3 repeats row 2 (its results are not used).
+        // The slot-0 point of the sample comes through the neighbor table itself: empty -> point 0, like every empty slot
+        const int r = si / a.SR, fr = q < 3 ? q : 2;
+        const int ps_ = a.pidx[(long long)si * a.Kstride], ps = ps_ > 0 ? ps_ : 0;
+        const float *fp = frames + (long long)p * 9 + 3 * fr, *gp = frames + (long long)ps * 9 + 3 * fr;
+        G.fx = fp[0]; G.fy = fp[1]; G.fz = fp[2];
+        G.gx = gp[0]; G.gy = gp[1]; G.gz = gp[2];
+        G.dxv = a.dir[3 * p]; G.dyv = a.dir[3 * p + 1]; G.dzv = a.dir[3 * p + 2];
+        G.rx = a.raydir[3 * r]; G.ry = a.raydir[3 * r + 1]; G.rz = a.raydir[3 * r + 2];
+        if (q == 0) { G.cx = a.color[3 * p]; G.cy = a.color[3 * p + 1]; G.cz = a.color[3 * p + 2]; }
+    } else if (q == 0) {
         const int r = si / a.SR;
         G.dxv = a.dir[3 * p]; G.dyv = a.dir[3 * p + 1]; G.dzv = a.dir[3 * p + 2];
         G.cx = a.color[3 * p]; G.cy = a.color[3 * p + 1]; G.cz = a.color[3 * p + 2];
@@ -546,7 +563,10 @@ __device__ __forceinline__ void f_gather(const FwdArgs &a, FGather &G, int si_, 
 // (point_aggregators.py:773-784, :425-428, :506, :566; networks.py:175-190)
 // MIX: the tile in the mixed format of mixq.h (columns < 256: h plane + e4m3 units; from 256 on the two f16 planes, h to nearest)
 // HR: f16x3.h's two planes with h rounded to NEAREST (the training forward: its k-major copy-outs then read the h plane only)
-template <bool PERS, bool MIX = false, bool HR = false>
+// FRAMES: per-point Rw2c (scene editing, point_aggregators.py:492-496,506,526,566): the first three distance components and the stored
+// direction are rotated by the frame of the ROW's point, the view direction by the frame of the sample's SLOT-0 point -- also inside the
+// extras (q - v, q.v) of every row of the sample, which so mix two frames exactly as the reference does
+template <bool PERS, bool MIX = false, bool HR = false, bool FRAMES = false>
 __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char *X, float *exb, float *wraw, int *sidx, int si, int p, int row, int q) {
     const float dwx = G.px - G.lx, dwy = G.py - G.ly, dwz = G.pz - G.lz;
     float ppx, ppy, pcz, spx, spy, scz;
@@ -554,12 +574,29 @@ __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char
         ppx = G.ppx; ppy = G.ppy; pcz = G.ppz; spx = G.lpx; spy = G.lpy; scz = G.lpz;
     } else {
         float pcx, pcy, scx, scy;
+        if (FRAMES) {
+            // hipcc contracts a sum of three products into a multiply and two FMAs in an order that depends on the code around it (in the uniform
+            // instance the first of the two rot3 below starts from the x product, the second from the y product), and each order rounds
+            // differently.  The FRAMES instances spell out the order the uniform fused-path instance has -- here, at the row weight and at q.v
+            // below -- so that identity frames reproduce the uniform render bit for bit (tests/test_gpu_editing.py)
+            const float *M = a.cam.camrot;
+            const float x = G.px - a.cam.campos[0], y = G.py - a.cam.campos[1], z = G.pz - a.cam.campos[2];
+            const float u = G.lx - a.cam.campos[0], v = G.ly - a.cam.campos[1], w = G.lz - a.cam.campos[2];
+            pcx = __builtin_fmaf(z, M[6], __builtin_fmaf(y, M[3], x * M[0]));
+            pcy = __builtin_fmaf(z, M[7], __builtin_fmaf(y, M[4], x * M[1]));
+            pcz = __builtin_fmaf(z, M[8], __builtin_fmaf(y, M[5], x * M[2]));
+            scx = __builtin_fmaf(w, M[6], __builtin_fmaf(u, M[0], v * M[3]));
+            scy = __builtin_fmaf(w, M[7], __builtin_fmaf(u, M[1], v * M[4]));
+            scz = __builtin_fmaf(w, M[8], __builtin_fmaf(u, M[2], v * M[5]));
+        } else {
         rot3(a.cam.camrot, G.px - a.cam.campos[0], G.py - a.cam.campos[1], G.pz - a.cam.campos[2], false, pcx, pcy, pcz);
         rot3(a.cam.camrot, G.lx - a.cam.campos[0], G.ly - a.cam.campos[1], G.lz - a.cam.campos[2], false, scx, scy, scz);
+        }
         ppx = pcx / pcz; ppy = pcy / pcz; spx = scx / scz; spy = scy / scz;
     }
     float d0, d1, d2;
-    rot3(a.cam.rw2c, dwx, dwy, dwz, true, d0, d1, d2);
+    if (FRAMES) d0 = d1 = d2 = dwx * G.fx + dwy * G.fy + dwz * G.fz;        // the thread's own component (q < 3)
+    else rot3(a.cam.rw2c, dwx, dwy, dwz, true, d0, d1, d2);
     const float d3 = ppx * pcz - spx * scz, d4 = ppy * pcz - spy * scz, d5 = pcz - scz;
     const float da = q == 0 ? d0 : q == 1 ? d1 : q == 2 ? d2 : d3;
     const float db = q == 0 ? d4 : d5;
@@ -617,14 +654,29 @@ __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char
         if (MIX || HR) pn_xt_store4(X, row, PN_ONES1, 1.f, 0.f, 0.f, 0.f);
         else pn_x_store4<false>(X, row, PN_ONES1, 1.f, 0.f, 0.f, 0.f);
     }
+    float fvx = 0.f, fvy = 0.f, fvz = 0.f, fqx = 0.f, fqy = 0.f, fqz = 0.f;
+    if (FRAMES) {          // components q of the rotated view and point directions -> thread 0 of the row (lanes l, l + 1, l + 2 hold q = 0, 1, 2)
+        fvx = G.rx * G.gx + G.ry * G.gy + G.rz * G.gz;
+        fqx = G.dxv * G.fx + G.dyv * G.fy + G.dzv * G.fz;
+        fvy = __shfl_down(fvx, 1, 64); fvz = __shfl_down(fvx, 2, 64);
+        fqy = __shfl_down(fqx, 1, 64); fqz = __shfl_down(fqx, 2, 64);
+    }
     if (q == 0) {
         float vx, vy, vz, qx, qy, qz;
+        if (FRAMES) { vx = fvx; vy = fvy; vz = fvz; qx = fqx; qy = fqy; qz = fqz; }
+        else {
         rot3(a.cam.rw2c, G.rx, G.ry, G.rz, true, vx, vy, vz);
         rot3(a.cam.rw2c, G.dxv, G.dyv, G.dzv, true, qx, qy, qz);
+        }
         float *ex = exb + row * 8;
         *reinterpret_cast<float4 *>(ex) = make_float4(G.cx, G.cy, G.cz, qx - vx);
+        if (FRAMES) {          // (the same sums in the uniform instance's order of products: see above)
+            *reinterpret_cast<float4 *>(ex + 4) = make_float4(qy - vy, qz - vz, __builtin_fmaf(qz, vz, __builtin_fmaf(qx, vx, qy * vy)), 1.f);
+            wraw[row] = p >= 0 ? 1.0f / fmaxf(sqrtf(__builtin_fmaf(dwz, dwz, __builtin_fmaf(dwx, dwx, dwy * dwy))), 1e-6f) : 0.f;
+        } else {
         *reinterpret_cast<float4 *>(ex + 4) = make_float4(qy - vy, qz - vz, qx * vx + qy * vy + qz * vz, 1.f);
         wraw[row] = p >= 0 ? 1.0f / fmaxf(sqrtf(dwx * dwx + dwy * dwy + dwz * dwz), 1e-6f) : 0.f;
+        }
         sidx[row] = si;
     }
 }
@@ -783,9 +835,11 @@ PN_TR_DECL(pn_trace_fwd);
 #endif
 // WG2: the two-plane weight-gradient mode (pnerf_set_wgrad_planes(2)): every saved GEMM operand also leaves its residual plane, X0 whole
 // NP = 4: the mixed format of mixq.h (f16 h.h + e4m3 cross terms: the default since round 6); NP = 3 / 2: f16x3.h's three / two f16 products
-template <bool TRAIN, bool PERS, int NP, bool WG2 = false>
-__global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
+// FRAMES: per-point Rw2c frames (a.frames; inference only, f16 cross terms and three products)
+template <bool TRAIN, bool PERS, int NP, bool WG2 = false, bool FRAMES = false>
+__global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename FwdArgsOf<FRAMES>::type a) {
     constexpr bool MIX = NP == 4;
+    static_assert(!FRAMES || (!TRAIN && NP == 3), "per-point frames: the default inference arithmetic only");
     constexpr bool HR = !MIX;                       // f16x3 tiles with h rounded to nearest (inference and training alike: the same bits); training: h-only copy-outs
     constexpr bool HC = TRAIN && !WG2;              // the k-major copy-outs read the h plane alone
     constexpr int NPC = MIX ? 3 : NP;          // (what the classic templates are instantiated with where MIX compiles them away)
@@ -796,6 +850,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
     float *exb = reinterpret_cast<float *>(smem_f + FL_EX), *w5s = reinterpret_cast<float *>(smem_f + FL_W5);
     float *wraw = reinterpret_cast<float *>(smem_f + FL_ROW), *wrow = wraw + PN_TILE, *wnrm = wrow + PN_TILE;
     int *sidx = reinterpret_cast<int *>(wnrm + PN_TILE);
+    const float *frames = nullptr;
+    if constexpr (FRAMES) frames = a.frames;
     const int tid0 = threadIdx.x;
     const int K = a.K, TS = a.TS;
     const unsigned kinv = pn_kinv(K);
@@ -824,7 +880,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         si2 = tile + 2 * stride < tile_last ? f_sample_of(a, tile + 2 * stride, row, Ns, kinv) : -1;
         p0 = si0 >= 0 ? a.pidx[(long long)si0 * a.Kstride + k] : -1;
         p1 = si1 >= 0 ? a.pidx[(long long)si1 * a.Kstride + k] : -1;
-        f_gather<PERS>(a, G, si0, p0, q);
+        f_gather<PERS, FRAMES>(a, G, si0, p0, q, frames);
     }
 
     f32x16 acc[PN_NFB][2];
@@ -840,7 +896,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         const long long gtile = tb + tile;               // tile index inside the saved area
         PN_LDS_BARRIER();                                 // the previous tile's readers are done with X and the row arrays
         PN_TR(pn_trace_fwd, 0); PN_TR_HWID(pn_trace_fwd);
-        f_build<PERS, MIX, HR>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
+        f_build<PERS, MIX, HR, FRAMES>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
         // Round 4: what the next GEMM needs from GLOBAL memory -- its bias (the accumulators' initial value) and its first weight-fragment
         // chunks -- is requested in front of the barrier that precedes it, not behind: neither depends on LDS, and the L2 round trip
         // (0.6 .. 1.1 us per layer in profiles/r03_phase_trace.json: the "acc = bias" phases) passes under the barrier wait.
@@ -957,7 +1013,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(FwdArgs a) {
         const float cf_cur = G.cf;
         (void)cf_cur;
         const int si_next = si1, p_next = p1;
-        if (tile + stride < tile_last) f_gather<PERS>(a, G, si1, p1, q);
+        if (tile + stride < tile_last) f_gather<PERS, FRAMES>(a, G, si1, p1, q, frames);
         const int p2 = si2 >= 0 ? a.pidx[(long long)si2 * a.Kstride + k] : -1;
         const int si3 = tile + 3 * stride < tile_last ? f_sample_of(a, tile + 3 * stride, row, Ns, kinv) : -1;
         PN_LDS_BARRIER();
@@ -1058,8 +1114,9 @@ __device__ __forceinline__ void c_acc_zero(f32x16 (&acc)[2][2]) {
         for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
 }
 
-template <bool TRAIN, int NP, bool WG2 = false>
-__global__ __launch_bounds__(256, 2) void k_color_forward(FwdArgs a) {
+// FRAMES: the view direction is rotated by the frame of the sample's slot-0 point (a.frames) instead of cam.rw2c
+template <bool TRAIN, int NP, bool WG2 = false, bool FRAMES = false>
+__global__ __launch_bounds__(256, 2) void k_color_forward(typename FwdArgsOf<FRAMES>::type a) {
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     char *X = smem_c;
     float *w4s = reinterpret_cast<float *>(smem_c + CL_W4);       // [3][128] output layer
@@ -1095,6 +1152,12 @@ __global__ __launch_bounds__(256, 2) void k_color_forward(FwdArgs a) {
                 // thread q < 3 of the row: direction component q, its four frequencies (columns 256 + 4 q .. and 268 + 4 q ..)
                 const int r = si / a.SR;
                 float v[3], sn[4], cs[4];
+                if constexpr (FRAMES) {
+                    const int ps_ = a.pidx[(long long)si * a.Kstride], ps = ps_ > 0 ? ps_ : 0;
+                    const float *fp = a.frames + (long long)ps * 9;
+                    const float fm[9] = {fp[0], fp[1], fp[2], fp[3], fp[4], fp[5], fp[6], fp[7], fp[8]};
+                    rot3(fm, a.raydir[3 * r], a.raydir[3 * r + 1], a.raydir[3 * r + 2], true, v[0], v[1], v[2]);
+                } else
                 rot3(a.cam.rw2c, a.raydir[3 * r], a.raydir[3 * r + 1], a.raydir[3 * r + 2], true, v[0], v[1], v[2]);
                 const float vq = q == 0 ? v[0] : (q == 1 ? v[1] : v[2]);
                 pn_pe_octaves<4>(vq, sn, cs);
@@ -1234,6 +1297,8 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     a.R = R; a.SR = SR; a.K = K; a.TS = pn_tile_samples(K);
     a.cap_samples = cap_samples;
     a.decoded = d_decoded; a.weight = d_weight; a.sv = sv;
+    const bool frames = pts->frames != nullptr;
+    if (frames && train) return PNERF_E_INVAL;            // per-point frames are render-only (include/pnerf.h: pnerf_points.frames)
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) != hipSuccess) return PNERF_E_LAUNCH;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 256;
@@ -1243,8 +1308,12 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     const bool pers = d_xyz_pers != nullptr;
     const bool np2 = !train && pn_inference_products == 2;      // inference with the weights' high plane only (f16x3.h: NP)
     const bool mix = !wg2 && !np2 && (pn_mix_mask() & (train ? 2 : 1));      // mixq.h: f16 h.h + e4m3 cross terms
+    if (frames && (np2 || mix)) return PNERF_E_UNSUP;     // the FRAMES instances exist for the default inference arithmetic only
     // the one place that names the kernel instances: the selection serves both the LDS attribute and the launch
     using FwdKernel = void (*)(FwdArgs);
+    using FwdKernelF = void (*)(FwdArgsF);            // per-point frames: their own argument and instances
+    const FwdKernelF kfnf = pers ? k_agg_forward<false, true, 3, false, true> : k_agg_forward<false, false, 3, false, true>;
+    const FwdKernelF cfnf = k_color_forward<false, 3, false, true>;
     const FwdKernel kfn = wg2   ? (pers ? k_agg_forward<true, true, 3, true> : k_agg_forward<true, false, 3, true>)
                         : mix   ? (train ? (pers ? k_agg_forward<true, true, 4> : k_agg_forward<true, false, 4>)
                                          : (pers ? k_agg_forward<false, true, 4> : k_agg_forward<false, false, 4>))
@@ -1252,8 +1321,8 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
                         : np2   ? (pers ? k_agg_forward<false, true, 2> : k_agg_forward<false, false, 2>)
                                 : (pers ? k_agg_forward<false, true, 3> : k_agg_forward<false, false, 3>);
     const FwdKernel cfn = wg2 ? k_color_forward<true, 3, true> : train ? k_color_forward<true, 3> : np2 ? k_color_forward<false, 2> : k_color_forward<false, 3>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(cfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipFuncSetAttribute(frames ? reinterpret_cast<const void *>(kfnf) : reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipFuncSetAttribute(frames ? reinterpret_cast<const void *>(cfnf) : reinterpret_cast<const void *>(cfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
     int rc = pn_classify(sv, d_valid_list, d_counters, d_sample_pidx, K, cap_samples, train, save_x0, s);
     if (rc) return rc;
     a.cls_list = sv.cls_list; a.cls_info = sv.cls_info; a.Kstride = K;
@@ -1265,13 +1334,15 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
             a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
             const long long tiles = (cap_samples + a.TS - 1) / a.TS;
             const int grid_a = (int)(tiles < 2LL * ncu ? (tiles > 0 ? tiles : 1) : 2LL * ncu);     // two workgroups per CU
-            hipLaunchKernelGGL(kfn, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
+            if (frames) { FwdArgsF af; static_cast<FwdArgs &>(af) = a; af.frames = pts->frames; hipLaunchKernelGGL(kfnf, dim3(grid_a), dim3(PN_NTHR), lds_a, s, af); }
+            else hipLaunchKernelGGL(kfn, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
         }
     }
     a.K = K; a.TS = pn_tile_samples(K); a.valid_list = sv.cls_list;      // the colour MLP walks the class-ordered list: f rows are in that order
     {
         PnProfScope prof(PNK_COLOR_FWD, s);
-        hipLaunchKernelGGL(cfn, dim3(grid_c), dim3(256), lds_c, s, a);
+        if (frames) { FwdArgsF af; static_cast<FwdArgs &>(af) = a; af.frames = pts->frames; hipLaunchKernelGGL(cfnf, dim3(grid_c), dim3(256), lds_c, s, af); }
+        else hipLaunchKernelGGL(cfn, dim3(grid_c), dim3(256), lds_c, s, a);
     }
     PN_CHECK_LAUNCH();
     return 0;

@@ -27,7 +27,9 @@ struct PnProbeOut {
     float *max_opacity, *loc3, *far_dist, *avg_color3, *avg_dir3, *avg_conf, *avg_emb32;
 };
 
-__global__ __launch_bounds__(PN_PR_TPB) void k_probe_rays(pnerf_points pts, const float *__restrict__ opacity, const float *__restrict__ weight,
+// what the kernel reads of pnerf_points (the probe outputs do not depend on per-point frames)
+struct PrPoints { const float *xyz, *embedding, *conf, *dir, *color; int32_t n, feat_dim; };
+__global__ __launch_bounds__(PN_PR_TPB) void k_probe_rays(PrPoints pts, const float *__restrict__ opacity, const float *__restrict__ weight,
                                                           const float *__restrict__ sample_loc, const int *__restrict__ sample_pidx,
                                                           const int *__restrict__ ray_hit, int R, int SR, int K, PnProbeOut o) {
     const int lane = threadIdx.x & 63;
@@ -135,7 +137,7 @@ extern "C" int pnerf_probe_rays(const pnerf_points *pts, const float *d_opacity,
         !d_avg_dir3 || !d_avg_conf || !d_avg_emb32) return PNERF_E_INVAL;
     if (pts->feat_dim != PN_PR_EMB) return PNERF_E_UNSUP;
     PnProbeOut o = {d_max_opacity, d_loc3, d_far_dist, d_avg_color3, d_avg_dir3, d_avg_conf, d_avg_emb32};
-    hipLaunchKernelGGL(k_probe_rays, dim3(pn_cdiv(R, PN_PR_TPB / 64)), dim3(PN_PR_TPB), 0, (hipStream_t)stream, *pts, d_opacity, d_weight,
+    hipLaunchKernelGGL(k_probe_rays, dim3(pn_cdiv(R, PN_PR_TPB / 64)), dim3(PN_PR_TPB), 0, (hipStream_t)stream, PrPoints{pts->xyz, pts->embedding, pts->conf, pts->dir, pts->color, pts->n, pts->feat_dim}, d_opacity, d_weight,
                        d_sample_loc, d_sample_pidx, d_ray_hit, R, SR, K, o);
     PN_CHECK_LAUNCH();
     return 0;

@@ -464,6 +464,7 @@ extern "C" int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points 
     if (rc) return rc;
     if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_sample_nn || !d_valid_list || !d_counters) return PNERF_E_INVAL;
     if (!d_decoded || !d_weight || !d_ray_color || !d_opacity || !d_bg_trans || !d_blend_w) return PNERF_E_INVAL;
+    if (pts->frames && d_saved) return PNERF_E_INVAL;      // per-point frames are render-only
     if (R == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     PnSaved sv;
@@ -504,6 +505,7 @@ extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points
     if (rc) return rc;
     if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_sample_nn || !d_valid_list || !d_counters) return PNERF_E_INVAL;
     if (!d_decoded || !d_weight || !d_grad_ray_color || !d_saved || !d_grad_params || !pg || !d_ws) return PNERF_E_INVAL;
+    if (pts->frames) return PNERF_E_INVAL;                 // per-point frames are render-only
     const size_t gd_bytes = pn_align((size_t)R * SR * 4 * sizeof(float));
     if (ws_bytes < gd_bytes + pn_wgrad_partials_bytes()) return PNERF_E_WS;
     if (R == 0 || n_valid == 0) return 0;
@@ -549,6 +551,7 @@ extern "C" int pnerf_agg_forward(const pnerf_camera *cam, const pnerf_points *pt
     if (rc) return rc;
     if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_valid_list || !d_counters || !d_decoded || !d_weight) return PNERF_E_INVAL;
     if ((d_xyz_pers == nullptr) != (d_loc_pers == nullptr)) return PNERF_E_INVAL;
+    if (pts->frames && d_saved) return PNERF_E_INVAL;      // per-point frames are render-only
     if (R == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     PnSaved sv;
@@ -577,6 +580,7 @@ extern "C" int pnerf_agg_backward(const pnerf_camera *cam, const pnerf_points *p
     if (rc) return rc;
     if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_valid_list || !d_counters) return PNERF_E_INVAL;
     if (!d_decoded || !d_weight || !d_grad_decoded || !d_saved || !d_grad_params || !pg || !d_ws) return PNERF_E_INVAL;
+    if (pts->frames) return PNERF_E_INVAL;                 // per-point frames are render-only
     if (ws_bytes < pn_wgrad_partials_bytes()) return PNERF_E_WS;
     if (R == 0 || n_valid == 0) return 0;
     PnSaved sv = pn_saved_carve(d_saved, n_valid, K);

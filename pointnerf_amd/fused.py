@@ -58,7 +58,9 @@ class FusedRender(torch.autograd.Function):
         # (the C structure holds raw pointers: keep the arrays it points to alive until the backward has read them)
         ctx.point_arrays = (emb.detach().reshape(-1, emb.shape[-1]), conf.detach().reshape(-1, 1), pdir.detach().reshape(-1, 3),
                             color.detach().reshape(-1, 3))
-        pts = ops.make_points(env["xyz"], *ctx.point_arrays)
+        if env.get("frames") is not None and env["train"]:
+            raise NotImplementedError("per-point Rw2c (scene editing) is render-only: no training forward, no backward")
+        pts = ops.make_points(env["xyz"], *ctx.point_arrays, frames=env.get("frames"))
         # a step whose saved activations would exceed the arena budget runs its forward without saving anything; the backward then
         # re-runs the forward chunk of rays by chunk of rays (ops.arena_budget_bytes)
         ctx.recompute = bool(env["train"]) and L.lib().pnerf_agg_saved_bytes(env["n_valid"], env["K"]) > ops.arena_budget_bytes()
@@ -207,7 +209,9 @@ class Aggregate(torch.autograd.Function):
         # (the C structure holds raw pointers: the per-slot arrays must stay alive until the backward has read them)
         slot_arrays = (emb.detach().reshape(-1, emb.shape[-1]).contiguous(), conf.detach().reshape(-1, 1).contiguous(),
                        pdir.detach().reshape(-1, 3).contiguous(), color.detach().reshape(-1, 3).contiguous())
-        pts = ops.make_points(env["xyz_slots"], *slot_arrays)
+        if env.get("frames") is not None and env["train"]:
+            raise NotImplementedError("per-point Rw2c (scene editing) is render-only: no training forward, no backward")
+        pts = ops.make_points(env["xyz_slots"], *slot_arrays, frames=env.get("frames"))
         f32 = dict(dtype=torch.float32, device=dev)
         decoded, weight = torch.empty(R, SR, 4, **f32), torch.empty(R, SR, K, **f32)
         saved = ws = None

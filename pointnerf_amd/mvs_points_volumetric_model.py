@@ -407,8 +407,9 @@ class MvsPointsVolumetricModel:
     # ------------------------------------------------------------------ point-cloud mutators (mvs_points_volumetric_model.py:172-182,240-242)
     def set_points(self, points_xyz, points_embedding, points_color=None, points_dir=None, points_conf=None, Rw2c=None, eulers=None,
                    editing=False):
-        if editing:
-            raise NotImplementedError("editing_set_points (scene editing) is outside the hot path's callers")
+        if editing:                 # a composed scene (run/editing.py:211; pointnerf_amd.editing.compose_parts): render-only, per-point Rw2c
+            return self.neural_points.editing_set_points(points_xyz, points_embedding, points_color=points_color, points_dir=points_dir,
+                                                         points_conf=points_conf, parameter=self.opt.feedforward == 0, Rw2c=Rw2c, eulers=eulers)
         self.neural_points.set_points(points_xyz, points_embedding, points_color=points_color, points_dir=points_dir,
                                       points_conf=points_conf, parameter=self.opt.feedforward == 0, Rw2c=Rw2c, eulers=eulers)
         if self.opt.feedforward == 0 and self.opt.is_train:

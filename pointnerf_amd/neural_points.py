@@ -8,6 +8,11 @@ kept verbatim, including the reference's spelling.
   query_dense(inputs)        -> the fused path's dense device tensors (no host sync)
   prune / grow_points / set_points / reset_querier : neural_points.py:341-467 (re-create the nn.Parameters,
                                 which also invalidates the cached voxel grid: the cache is keyed on the storage)
+  editing_set_points         -> neural_points.py:470-486: a composed scene (pointnerf_amd.editing.compose_parts), tensors kept as given
+
+``Rw2c`` is either ONE [3,3] frame (identity in every training script) or, for a composed scene, one frame PER POINT [N,3,3]
+(checkpoint key ``neural_points.Rw2c`` in both cases).  The per-point table follows the points through prune / grow_points, reaches the
+fused renderer as a device pointer and is render-only.
 """
 import numpy as np
 import torch
@@ -42,7 +47,7 @@ class NeuralPoints(nn.Module):
                     setattr(self, name, p)
             rw = get("Rw2c")
             if rw is not None:
-                self.Rw2c = nn.Parameter(rw.to(device)); self.Rw2c.requires_grad = False
+                self.Rw2c = nn.Parameter(self._check_frames(rw.to(device), self.xyz.shape[0])); self.Rw2c.requires_grad = False
             else:
                 self.Rw2c = torch.eye(3, device=device, dtype=torch.float32)
         self.reg_weight = reg_weight
@@ -73,8 +78,26 @@ class NeuralPoints(nn.Module):
             p.pnerf_point_xyz = True          # (optim.ShardedAdam refuses trainable positions: see there)
         return p
 
+    @staticmethod
+    def _check_frames(Rw2c, n_points):
+        """Rw2c is [3,3] or [N,3,3] with one frame per point: anything else would be read as something it is not"""
+        if Rw2c.dim() == 3 and tuple(Rw2c.shape) != (int(n_points), 3, 3) or Rw2c.dim() == 2 and tuple(Rw2c.shape) != (3, 3) \
+                or Rw2c.dim() not in (2, 3):
+            raise ValueError("NeuralPoints: Rw2c must be [3, 3] or [%d, 3, 3] (one frame per point), got %s" % (int(n_points), list(Rw2c.shape)))
+        return Rw2c
+
+    def _frozen(self, t):
+        p = nn.Parameter(t)
+        p.requires_grad = False
+        return p
+
     def prune(self, thresh):
         mask = self.points_conf[0, ..., 0] >= thresh
+        # per-point frames / eulers follow their points (neural_points.py:364-369); tensors given by editing_set_points stay tensors
+        for name in ("eulers", "Rw2c"):
+            t = getattr(self, name)
+            if isinstance(t, torch.Tensor) and t.dim() > (1 if name == "eulers" else 2):
+                setattr(self, name, self._frozen(t.detach()[mask]) if isinstance(t, nn.Parameter) else t[mask])
         self.xyz = self._param(self.xyz[mask, :], "xyz_grad")
         for name, flag in (("points_embeding", "feat_grad"), ("points_conf", "conf_grad"), ("points_dir", "dir_grad"),
                            ("points_color", "color_grad")):
@@ -85,6 +108,19 @@ class NeuralPoints(nn.Module):
         print("@@@@@@@@@  pruned {}/{}".format(torch.sum(mask == 0), mask.shape[0]))
 
     def grow_points(self, add_xyz, add_embedding, add_color, add_dir, add_conf, add_eulers=None, add_Rw2c=None):
+        # per-point frames / eulers: the new points' ROWS are appended (the reference concatenates ``add[None]`` along axis 1, which
+        # for a [N,3,3] table is the wrong axis and raises: neural_points.py:393-399); a cloud without per-point rows ignores the arguments
+        rows = []
+        for name, add, tail in (("eulers", add_eulers, 1), ("Rw2c", add_Rw2c, 2)):
+            t = getattr(self, name)
+            if isinstance(t, torch.Tensor) and t.dim() > tail:
+                if add is None or tuple(add.shape) != (int(add_xyz.shape[0]),) + tuple(t.shape[1:]):
+                    raise ValueError("grow_points: this cloud has per-point %s %s; add_%s must be [%d, %s]" % (
+                        name, list(t.shape), name, int(add_xyz.shape[0]), ", ".join(str(int(x)) for x in t.shape[1:])))
+                rows.append((name, t, add))
+        for name, t, add in rows:               # (nothing is changed before every argument has been checked)
+            new = torch.cat([t.detach(), add.to(device=t.device, dtype=t.dtype)], dim=0)
+            setattr(self, name, self._frozen(new) if isinstance(t, nn.Parameter) else new)
         self.xyz = self._param(torch.cat([self.xyz, add_xyz], dim=0), "xyz_grad")
         for name, flag, add in (("points_embeding", "feat_grad", add_embedding), ("points_conf", "conf_grad", add_conf),
                                 ("points_dir", "dir_grad", add_dir), ("points_color", "color_grad", add_color)):
@@ -117,8 +153,22 @@ class NeuralPoints(nn.Module):
         if Rw2c is None:
             self.Rw2c = torch.eye(3, device=points_xyz.device, dtype=points_xyz.dtype)
         else:
-            self.Rw2c = nn.Parameter(Rw2c)
+            self.Rw2c = nn.Parameter(self._check_frames(Rw2c, points_xyz.shape[0]))
             self.Rw2c.requires_grad = False
+
+    def editing_set_points(self, points_xyz, points_embeding, points_color=None, points_dir=None, points_conf=None, parameter=False,
+                           Rw2c=None, eulers=None):
+        """neural_points.py:470-486: the cloud of a composed scene (pointnerf_amd.editing.compose_parts).  Nothing is wrapped as a parameter --
+        editing renders, it never trains -- and Rw2c ([3,3], or one frame per point [N,3,3]) is kept as given."""
+        dc = getattr(self.opt, "default_conf", -1.0)
+        if dc > 0.0 and dc <= 1.0 and points_conf is not None:
+            points_conf = torch.ones_like(points_conf) * dc
+        rw = torch.eye(3, device=points_xyz.device, dtype=points_xyz.dtype) if Rw2c is None else self._check_frames(Rw2c, points_xyz.shape[0])
+        for name, t in (("xyz", points_xyz), ("points_embeding", points_embeding), ("points_dir", points_dir), ("points_conf", points_conf),
+                        ("points_color", points_color), ("Rw2c", rw)):
+            self._parameters.pop(name, None)      # (a model restored from a checkpoint holds nn.Parameters under these names; nn.Module refuses
+            setattr(self, name, t)                #  to put a plain tensor in a parameter's place)
+        self.invalidate_grid()
 
     # ------------------------------------------------------------------ hot path
     def w2pers(self, point_xyz, camrotc2w, campos):
@@ -159,6 +209,8 @@ class NeuralPoints(nn.Module):
         xc = torch.sum(xs[..., None, :] * torch.transpose(camrotc2w, 1, 2)[:, None, None, None, ...], dim=-1)
         sampled_xyz_pers = torch.stack([xc[..., 0] / xc[..., 2], xc[..., 1] / xc[..., 2], xc[..., 2]], dim=-1)
         sampled_Rw2c = self.Rw2c
+        if isinstance(sampled_Rw2c, torch.Tensor) and sampled_Rw2c.dim() == 3:      # one frame per point: gathered like the other rows (:717)
+            sampled_Rw2c = ops.gather_rows(sampled_Rw2c.detach().reshape(-1, 9), sample_pidx).view(B, R, SR, K, 3, 3)
         return g(self.points_color), sampled_Rw2c, g(self.points_dir), g(self.points_conf), g(self.points_embeding), \
             sampled_xyz_pers, sampled_xyz, sample_pnt_mask, sample_loc, sample_loc_w_tensor, sample_ray_dirs_tensor, \
             ray_mask_tensor, vsize, self.grid_vox_sz

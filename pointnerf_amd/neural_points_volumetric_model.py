@@ -71,6 +71,14 @@ class NeuralPointsRayMarching(nn.Module):
         train = torch.is_grad_enabled() if train is None else train
         # xyz_grad > 0: the point positions are a leaf of the fused step (d xyz from k_agg_backward's XYZG instances)
         xyz_leaf = bool(train) and npnt.xyz.requires_grad
+        # one Rw2c frame PER POINT (a composed scene, pointnerf_amd.editing): the table goes to the kernels as a device pointer
+        # (pnerf_points.frames) -- it is never read back to the host -- and is render-only, like the reference's frozen Rw2c
+        frames = None
+        if isinstance(npnt.Rw2c, torch.Tensor) and npnt.Rw2c.dim() == 3:
+            if train:
+                raise NotImplementedError("per-point Rw2c (scene editing) is render-only: run the forward under torch.no_grad() -- the reference "
+                                          "freezes Rw2c and editing never trains" + (" (xyz_grad > 0 included)" if xyz_leaf else ""))
+            frames = ops.frames_table(npnt.Rw2c, npnt.xyz.shape[0])
         R = raydir.reshape(-1, 3).shape[0]
         if train and self._pool_rays < R:              # worst case (every ray hits): ~16 live [R,SR,K] fp32 tensors around the loss
             ops.reserve_pool(16 * R * int(opt.SR) * int(opt.K) * 4, raydir.device)
@@ -85,7 +93,7 @@ class NeuralPointsRayMarching(nn.Module):
         plan = plan(dense) if (plan is not None and train) else None
         words = dense["counters"].to(torch.int64) if plan is None else torch.cat([dense["counters"].to(torch.int64), plan[1]])
         st = agg.mlp_state()
-        rw = ops.host_array(npnt.Rw2c) if isinstance(npnt.Rw2c, torch.Tensor) else None
+        rw = ops.host_array(npnt.Rw2c) if (isinstance(npnt.Rw2c, torch.Tensor) and frames is None) else None
         cam = ops.make_camera(ops.host_array(campos).reshape(-1)[:3], ops.host_array(camrotc2w).reshape(-1)[:9],
                               opt.vsize[2], opt.raydist_mode_unit,
                               bg=None if bg_color is None else ops.host_array(bg_color).reshape(-1)[:3], rw2c=rw)
@@ -97,6 +105,8 @@ class NeuralPointsRayMarching(nn.Module):
             env["zero_one_eps"] = float(zero_one_eps)
         if xyz_leaf:
             env["xyz_grad"] = True
+        if frames is not None:
+            env["frames"] = frames
         leaves = (npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + ((npnt.xyz,) if xyz_leaf else ()) + tuple(mlp_params)
         # The step's one host read (number of valid samples: sizes the activation arena; number of hit rays: shapes of the outputs).
         # Round 4: a TRAINING step whose arena already exists is enqueued BEFORE that read with the arena's capacity as the bound -- every

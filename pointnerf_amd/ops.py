@@ -221,13 +221,36 @@ def make_camera(campos, camrot, vsize_z, raydist_mode_unit=1, bg=None, rw2c=None
     return c
 
 
-def make_points(xyz, emb, conf, pdir, color):
+def frames_table(Rw2c, n_points):
+    """The [N,9] device view of a per-point Rw2c table [N,3,3] that pnerf_points.frames takes (no copy for a contiguous fp32 table; never a
+    host copy: the table is 72 MB at 2 M points).  Also refuses the arithmetic settings no FRAMES kernel instance exists for."""
+    _need_cuda(Rw2c, "Rw2c")
+    if Rw2c.dim() != 3 or tuple(Rw2c.shape) != (int(n_points), 3, 3):
+        raise ValueError("pointnerf_amd: per-point Rw2c must be [%d, 3, 3], got %s" % (int(n_points), list(Rw2c.shape)))
+    lib = L.lib()
+    products = lib.pnerf_set_inference_products(3)
+    lib.pnerf_set_inference_products(products)
+    if products != 3:
+        raise NotImplementedError("pointnerf_amd: per-point Rw2c is not implemented for set_inference_products(2) (pnerf_set_inference_products); "
+                                  "set it back to 3")
+    if cross_terms_state()[1] & 1:
+        raise NotImplementedError("pointnerf_amd: per-point Rw2c is not implemented for e4m3 cross terms in the inference forward (bit 0 of "
+                                  "set_cross_terms(8, where), pnerf_set_cross_terms_where); clear the bit")
+    return Rw2c.detach().reshape(-1, 9).contiguous().float()
+
+
+def make_points(xyz, emb, conf, pdir, color, frames=None):
+    """``frames``: optional [N,9] fp32 device table of per-point Rw2c frames (frames_table); the returned structure keeps it alive."""
     for n, t in (("xyz", xyz), ("points_embeding", emb), ("points_conf", conf), ("points_dir", pdir), ("points_color", color)):
         _need_cuda(t, n)
         assert t.is_contiguous() and t.dtype == torch.float32, n
     p = L.Points()
     p.xyz, p.embedding, p.conf, p.dir, p.color = xyz.data_ptr(), emb.data_ptr(), conf.data_ptr(), pdir.data_ptr(), color.data_ptr()
     p.n, p.feat_dim = int(xyz.reshape(-1, 3).shape[0]), int(emb.shape[-1])
+    if frames is not None:
+        _need_cuda(frames, "Rw2c frames")
+        assert frames.is_contiguous() and frames.dtype == torch.float32 and tuple(frames.shape) == (p.n, 9), "frames"
+        p.frames, p._frames_keep = frames.data_ptr(), frames
     return p
 
 

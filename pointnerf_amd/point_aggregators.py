@@ -135,15 +135,29 @@ class PointAggregator(nn.Module):
         in_shape = sample_loc_w.shape
         ray_valid = torch.any(sample_pnt_mask, dim=-1)
         dev = sampled_embedding.device
-        if R == 0 or not bool(ray_valid.any()):
+        # one Rw2c frame per gathered neighbor ([1,R,SR,K,3,3]: NeuralPoints.forward of a composed scene): render-only
+        frames = sampled_Rw2c is not None and sampled_Rw2c.dim() == 6
+        if sampled_Rw2c is not None and sampled_Rw2c.dim() != 2 and not frames:
+            raise NotImplementedError("Rw2c must be [3, 3] or the gathered per-point frames [1, R, SR, K, 3, 3], got %s" % list(sampled_Rw2c.shape))
+        if frames and (tuple(sampled_Rw2c.shape) != (B, R, SR, K, 3, 3) or torch.is_grad_enabled()):
+            raise NotImplementedError("per-point Rw2c (scene editing) is render-only: frames [1, R, SR, K, 3, 3] under torch.no_grad() -- the "
+                                      "reference freezes Rw2c and editing never trains")
+        # the route's one host read: is there a valid sample at all -- and, with per-point frames, one whose slot 0 is empty?  The kernels take
+        # the view direction's frame from slot 0 (point_aggregators.py:495); the query fills slots from 0 on, only a caller-made mask can
+        # leave it empty, and the slot-indexed pseudo points would then read ANOTHER sample's frame where the reference reads point 0's
+        if R == 0:
             return torch.zeros(in_shape[:-1] + (4,), device=dev, dtype=torch.float32), ray_valid, None, None
-        if sampled_Rw2c is not None and sampled_Rw2c.dim() != 2:
-            raise NotImplementedError("per-point Rw2c (normview) is not on the scripts' path")
+        flags = torch.stack([ray_valid.any(), (ray_valid & ~sample_pnt_mask[..., 0]).any() if frames else ray_valid.new_zeros(())]).tolist()
+        if not flags[0]:
+            return torch.zeros(in_shape[:-1] + (4,), device=dev, dtype=torch.float32), ray_valid, None, None
+        if flags[1]:
+            raise NotImplementedError("per-point Rw2c with a neighbor mask that leaves slot 0 of a valid sample empty (the query never does): the "
+                                      "view direction's frame is the one of slot 0")
         if sampled_color is None or sampled_dir is None or sampled_conf is None:
             raise NotImplementedError("point_color/dir/conf_mode must be '1' (lego script)")
         st = self.mlp_state()
         mlp_params, layout = self.ordered_params()
-        rw = None if sampled_Rw2c is None else sampled_Rw2c.detach().cpu().numpy()
+        rw = None if (sampled_Rw2c is None or frames) else sampled_Rw2c.detach().cpu().numpy()
         cam = ops.make_camera([0, 0, 0], np.eye(3), opt.vsize[2], 1, bg=None, rw2c=rw)     # camera unused: perspective coords supplied
         n_slots = R * SR * K
         slot = torch.arange(n_slots, dtype=torch.int32, device=dev).view(R, SR, K)
@@ -153,6 +167,8 @@ class PointAggregator(nn.Module):
                    loc_pers=c(sample_loc, 3), raydir=sample_ray_dirs[0, :, 0, :].detach().contiguous().float(), pidx=pidx,
                    nn=sample_pnt_mask[0].sum(-1).to(torch.int32).contiguous(), R=R, SR=SR, K=K, flat=st.flat,
                    packed=st.packed_image(), train=torch.is_grad_enabled(), layout=layout)
+        if frames:              # the frame table of the pseudo points: row si * K + k, like every other gathered array
+            env["frames"] = ops.frames_table(sampled_Rw2c.reshape(-1, 3, 3), n_slots)
         decoded, weight = Aggregate.apply(env, sampled_embedding, sampled_conf, sampled_dir, sampled_color, *mlp_params)
         conf_coefficient = gradient_clamp(sampled_conf[..., 0], lo=0.0001, hi=1)
         weight = weight.view(B, R, SR, K)
