@@ -247,6 +247,9 @@ int pnerf_set_cross_terms(int bits);
  * than the fp32 oracle's, which the gradient comparisons against the oracle see (bench.py reports that variant).  Returns the previous mask, or
  * PNERF_E_INVAL.  Process-wide. */
 int pnerf_set_cross_terms_where(int mask);
+/* The four settings above as they are now, without changing them: out = {inference products, weight-gradient planes, cross-term bits, the
+ * cross-term mask AS STORED} (the mask takes effect only while the cross-term bits are 8).  0, or PNERF_E_INVAL for a null pointer. */
+int pnerf_get_arithmetic(int32_t out[4]);
 
 /* Backward of pnerf_render_forward for dL/d(ray_color) = d_grad_ray_color [R,3]:
  * accumulates dL/d(MLP params) into d_grad_params (flat, pnerf_mlp_layout order) and

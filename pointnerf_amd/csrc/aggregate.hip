@@ -203,12 +203,7 @@ __global__ __launch_bounds__(256) void k_debug_mix_gemm(const float *__restrict_
     }
     __syncthreads();
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    pn_acc_zero(acc);
     pn_gemm_mix<PN_MIX_NS, NT, 8, 2>(X, img, 2 * wave, lane, acc);
 #pragma unroll
     for (int fb = 0; fb < 2; ++fb)
@@ -297,83 +292,62 @@ extern "C" int pnerf_debug_mfma_f16(const void *d_a, const void *d_b, float *d_o
 }
 
 // ------------------------------------------------------------------------------ saved activations
-size_t pn_saved_bytes(long long n_valid, int K, long long *rows_out, long long *samples_out) {
+// THE layout of the saved area: which arrays, in which order, how many elements each.  A carver without a base only counts (pn_saved_bytes), one
+// with a base hands out the pointers (pn_saved_carve): the two cannot disagree.  Returns the bytes.
+size_t pn_saved_walk(void *base, long long n_valid, int K, PnSaved &s) {
     const int TS = pn_tile_samples(K);
     // + PN_NCLS tiles of rounding (each class ends in a partial tile) + PN_NCLS gap tiles (every class owns a padding tile) + 1
     const long long tiles = (n_valid + TS - 1) / TS + 2 * PN_NCLS + 1;
-    const long long rows = tiles * PN_TILE;
-    const long long samples = ((tiles * TS + PN_CTILE - 1) / PN_CTILE + 1) * PN_CTILE;
-    if (rows_out) *rows_out = rows;
-    if (samples_out) *samples_out = samples;
-    size_t b = 0;
-    b += 2 * pn_align((size_t)rows / 8 * PN_NF1 * 16) + 2 * pn_align((size_t)rows / 8 * PN_H * 16);      // x0k, h2k | h1k, h3k (one plane)
-    b += 4 * pn_align((size_t)rows / 8 * PN_H * 16) + pn_align((size_t)rows * 32 * 32);                // dy1k..dy4k (one plane) | h4r
-    b += pn_align((size_t)rows * 4) + pn_align((size_t)rows * 16) + pn_align((size_t)tiles * 3 * 512 * 4) + pn_align(16);
-    b += pn_cls_bytes(samples);
-    b += 2 * pn_align((size_t)samples * PN_H * 4) + pn_align((size_t)samples * PN_HC * 4);                         // fs, dfs | c3
-    b += pn_align((size_t)samples / 8 * PN_NF1 * 16) + 2 * pn_align((size_t)samples / 8 * PN_HC * 16);              // xck | c1k, c2k (one plane)
-    b += 3 * pn_align((size_t)samples / 8 * PN_HC * 16) + pn_align((size_t)samples / PN_CTILE * 2 * 256 * 4);       // dc1k..dc3k | cmask
-    if (pn_wgrad_planes() == 2) {       // the residual planes of the fourteen streamed arrays
-        b += 2 * pn_align((size_t)rows / 8 * PN_NF1 * 16) + 6 * pn_align((size_t)rows / 8 * PN_H * 16);
-        b += pn_align((size_t)samples / 8 * PN_NF1 * 16) + 5 * pn_align((size_t)samples / 8 * PN_HC * 16);
-    }
-    return b;
-}
-
-PnSaved pn_saved_carve(void *base, long long n_valid, int K) {
-    PnSaved s;
-    size_t total = pn_saved_bytes(n_valid, K, &s.rows, &s.samples);
-    PnCarver cv(base, total);
-    const size_t rg = (size_t)s.rows / 8;
-    s.x0k = cv.take<uint4>(rg * PN_NF1); s.h2k = cv.take<uint4>(rg * PN_NF1);
-    s.h1k = cv.take<uint4>(rg * PN_H); s.h3k = cv.take<uint4>(rg * PN_H);
-    s.dy1k = cv.take<uint4>(rg * PN_H); s.dy2k = cv.take<uint4>(rg * PN_H);
-    s.dy3k = cv.take<uint4>(rg * PN_H); s.dy4k = cv.take<uint4>(rg * PN_H);
+    s.rows = tiles * PN_TILE;
+    s.samples = ((tiles * TS + PN_CTILE - 1) / PN_CTILE + 1) * PN_CTILE;
+    PnCarver cv(base);
+    const size_t rg = (size_t)s.rows / 8, rgc = (size_t)s.samples / 8;
+    // the k-major planes the weight-gradient GEMMs stream: the residual planes (two-plane mode only) repeat the layout of the first ones
+    auto planes = [&](uint4 *&x0, uint4 *&h2, uint4 *&h1, uint4 *&h3, uint4 *&dy1, uint4 *&dy2, uint4 *&dy3, uint4 *&dy4) {
+        x0 = cv.take<uint4>(rg * PN_NF1); h2 = cv.take<uint4>(rg * PN_NF1);
+        h1 = cv.take<uint4>(rg * PN_H); h3 = cv.take<uint4>(rg * PN_H);
+        dy1 = cv.take<uint4>(rg * PN_H); dy2 = cv.take<uint4>(rg * PN_H);
+        dy3 = cv.take<uint4>(rg * PN_H); dy4 = cv.take<uint4>(rg * PN_H);
+    };
+    auto cplanes = [&](uint4 *&xc, uint4 *&c1, uint4 *&c2, uint4 *&dc1, uint4 *&dc2, uint4 *&dc3) {
+        xc = cv.take<uint4>(rgc * PN_NF1); c1 = cv.take<uint4>(rgc * PN_HC); c2 = cv.take<uint4>(rgc * PN_HC);
+        dc1 = cv.take<uint4>(rgc * PN_HC); dc2 = cv.take<uint4>(rgc * PN_HC); dc3 = cv.take<uint4>(rgc * PN_HC);
+    };
+    planes(s.x0k, s.h2k, s.h1k, s.h3k, s.dy1k, s.dy2k, s.dy3k, s.dy4k);
     s.h4r = cv.take<uint4>((size_t)s.rows * 32 * 2);
     s.arow = cv.take<float>((size_t)s.rows); s.rmeta = cv.take<int4>((size_t)s.rows);
-    s.lmask = cv.take<unsigned>((size_t)(s.rows / PN_TILE) * 3 * 512);
+    s.lmask = cv.take<unsigned>((size_t)tiles * 3 * 512);
     s.gscale = cv.take<unsigned>(4);
     s.fs = cv.take<float>((size_t)s.samples * PN_H); s.dfs = cv.take<float>((size_t)s.samples * PN_H);
     s.c3 = cv.take<float>((size_t)s.samples * PN_HC);
-    const size_t rgc = (size_t)s.samples / 8;
-    s.xck = cv.take<uint4>(rgc * PN_NF1); s.c1k = cv.take<uint4>(rgc * PN_HC); s.c2k = cv.take<uint4>(rgc * PN_HC);
-    s.dc1k = cv.take<uint4>(rgc * PN_HC); s.dc2k = cv.take<uint4>(rgc * PN_HC); s.dc3k = cv.take<uint4>(rgc * PN_HC);
+    cplanes(s.xck, s.c1k, s.c2k, s.dc1k, s.dc2k, s.dc3k);
     s.cmask = cv.take<unsigned>((size_t)s.samples / PN_CTILE * 2 * 256);
-    s.wg2 = pn_wgrad_planes() == 2 ? 1 : 0;
+    s.wg2 = pn_arith().wgrad_planes == 2 ? 1 : 0;
     s.x0m = s.h1m = s.h2m = s.h3m = s.dy1m = s.dy2m = s.dy3m = s.dy4m = nullptr;
     s.xcm = s.c1m = s.c2m = s.dc1m = s.dc2m = s.dc3m = nullptr;
     if (s.wg2) {
-        s.x0m = cv.take<uint4>(rg * PN_NF1); s.h2m = cv.take<uint4>(rg * PN_NF1);
-        s.h1m = cv.take<uint4>(rg * PN_H); s.h3m = cv.take<uint4>(rg * PN_H);
-        s.dy1m = cv.take<uint4>(rg * PN_H); s.dy2m = cv.take<uint4>(rg * PN_H);
-        s.dy3m = cv.take<uint4>(rg * PN_H); s.dy4m = cv.take<uint4>(rg * PN_H);
-        s.xcm = cv.take<uint4>(rgc * PN_NF1); s.c1m = cv.take<uint4>(rgc * PN_HC); s.c2m = cv.take<uint4>(rgc * PN_HC);
-        s.dc1m = cv.take<uint4>(rgc * PN_HC); s.dc2m = cv.take<uint4>(rgc * PN_HC); s.dc3m = cv.take<uint4>(rgc * PN_HC);
+        planes(s.x0m, s.h2m, s.h1m, s.h3m, s.dy1m, s.dy2m, s.dy3m, s.dy4m);
+        cplanes(s.xcm, s.c1m, s.c2m, s.dc1m, s.dc2m, s.dc3m);
     }
-    pn_cls_carve(cv.take<char>(pn_cls_bytes(s.samples)), s.samples, s);
-    return s;
+    pn_cls_walk(cv, s);
+    return cv.off;
 }
-
-size_t pn_cls_bytes(long long samples) {
-    return pn_align((size_t)samples * 4) + pn_align(PN_CI_WORDS * 4) + pn_align(((size_t)2 * samples + pn_scan_scratch_ints(samples) + 8) * 4);
-}
-void pn_cls_carve(void *base, long long samples, PnSaved &s) {
-    PnCarver cv(base, pn_cls_bytes(samples));
-    s.cls_list = cv.take<int>((size_t)samples);
+// the class partition's arrays for s.samples samples (the tail of the saved area, and of the inference workspace: render.hip)
+void pn_cls_walk(PnCarver &cv, PnSaved &s) {
+    s.cls_list = cv.take<int>((size_t)s.samples);
     s.cls_info = cv.take<int>(PN_CI_WORDS);
-    s.cls_tmp = cv.take<int>((size_t)2 * samples + pn_scan_scratch_ints(samples) + 8);
+    s.cls_tmp = cv.take<int>((size_t)2 * s.samples + pn_scan_scratch_ints(s.samples) + 8);
 }
+size_t pn_saved_bytes(long long n_valid, int K) { PnSaved s; return pn_saved_walk(nullptr, n_valid, K, s); }
+PnSaved pn_saved_carve(void *base, long long n_valid, int K) { PnSaved s; pn_saved_walk(base, n_valid, K, s); return s; }
 
 extern "C" size_t pnerf_agg_saved_bytes(int64_t n_valid_samples, int K) {
     if (K <= 0 || K > PNERF_MAX_K || n_valid_samples < 0) return 0;
-    return pn_saved_bytes(n_valid_samples, K, nullptr, nullptr);
+    return pn_saved_bytes(n_valid_samples, K);
 }
 
 // ------------------------------------------------------------------------------ forward kernels
 namespace {
-constexpr int TPR = PN_TPR; // threads per tile row in the element-wise phases
-constexpr int EPT = PN_F / TPR;              // embedding dims per thread in the feature build
-
 struct FwdArgs {
     pnerf_camera cam;
     const float *xyz, *emb, *conf, *dir, *color;
@@ -395,18 +369,6 @@ struct FwdArgs {
 struct FwdArgsF : FwdArgs { const float *frames; };
 template <bool FRAMES> struct FwdArgsOf { using type = FwdArgs; };
 template <> struct FwdArgsOf<true> { using type = FwdArgsF; };
-
-__device__ __forceinline__ void rot3(const float *M /*row-major*/, float x, float y, float z, bool transpose, float &ox, float &oy, float &oz) {
-    // transpose=false: out_j = sum_i v_i M[i][j] (v @ M);  true: out_j = sum_i v_i M[j][i] (v @ M^T)
-    if (!transpose) { ox = x * M[0] + y * M[3] + z * M[6]; oy = x * M[1] + y * M[4] + z * M[7]; oz = x * M[2] + y * M[5] + z * M[8]; }
-    else { ox = x * M[0] + y * M[1] + z * M[2]; oy = x * M[3] + y * M[4] + z * M[5]; oz = x * M[6] + y * M[7] + z * M[8]; }
-}
-
-template <int N> __device__ __forceinline__ float group_sum(float v) {      // sum over N adjacent lanes (N = 4 or 8)
-#pragma unroll
-    for (int off = 1; off < N; off <<= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ------------------------------------------------------------------------------ sample classes
 // 6 % of the neighbor rows of valid samples are empty slots (a sample near the surface's edge has 1..K-1 neighbors); the
@@ -530,7 +492,7 @@ __device__ __forceinline__ int f_sample_of(const FwdArgs &a, long long tile, int
 template <bool PERS, bool FRAMES = false>
 __device__ __forceinline__ void f_gather(const FwdArgs &a, FGather &G, int si_, int p_, int q, const float *frames = nullptr) {
     const int p = p_ > 0 ? p_ : 0, si = si_ > 0 ? si_ : 0;     // empty slots / rows read point 0 / sample 0 like the reference (neural_points.py:709); their weight is 0
-    const float *ep = a.emb + (long long)p * PN_F + EPT * q;
+    const float *ep = a.emb + (long long)p * PN_F + PN_EPT * q;
     G.e0 = *reinterpret_cast<const float4 *>(ep); G.e1 = *reinterpret_cast<const float4 *>(ep + 4);
     G.px = a.xyz[3 * p]; G.py = a.xyz[3 * p + 1]; G.pz = a.xyz[3 * p + 2];
     G.lx = a.sample_loc[(long long)si * 3]; G.ly = a.sample_loc[(long long)si * 3 + 1]; G.lz = a.sample_loc[(long long)si * 3 + 2];
@@ -561,12 +523,12 @@ __device__ __forceinline__ void f_gather(const FwdArgs &a, FGather &G, int si_, 
 
 // X0 row of the tile: [e(32) | PE3(e) (192) | PE5(dists) (60) | 1 | 0 0 0], the row's raw weight and layer-3 extras
 // (point_aggregators.py:773-784, :425-428, :506, :566; networks.py:175-190)
-// MIX: the tile in the mixed format of mixq.h (columns < 256: h plane + e4m3 units; from 256 on the two f16 planes, h to nearest)
-// HR: f16x3.h's two planes with h rounded to NEAREST (the training forward: its k-major copy-outs then read the h plane only)
+// MIX: the tile in the mixed format of mixq.h (columns < 256: h plane + e4m3 units; from 256 on the two f16 planes, h to nearest); else
+// f16x3.h's two planes with h rounded to NEAREST (inference and training alike; the training forward's k-major copy-outs then read the h plane only)
 // FRAMES: per-point Rw2c (scene editing, point_aggregators.py:492-496,506,526,566): the first three distance components and the stored
 // direction are rotated by the frame of the ROW's point, the view direction by the frame of the sample's SLOT-0 point -- also inside the
 // extras (q - v, q.v) of every row of the sample, which so mix two frames exactly as the reference does
-template <bool PERS, bool MIX = false, bool HR = false, bool FRAMES = false>
+template <bool PERS, bool MIX = false, bool FRAMES = false>
 __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char *X, float *exb, float *wraw, int *sidx, int si, int p, int row, int q) {
     const float dwx = G.px - G.lx, dwy = G.py - G.ly, dwz = G.pz - G.lz;
     float ppx, ppy, pcz, spx, spy, scz;
@@ -603,12 +565,12 @@ __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char
     // the thread's 8 embedding dims and their 3 octaves
     const float e[8] = {G.e0.x, G.e0.y, G.e0.z, G.e0.w, G.e1.x, G.e1.y, G.e1.z, G.e1.w};
     if (MIX) {
-        pn_xq_store4(X, row, EPT * q, e[0], e[1], e[2], e[3]);
-        pn_xq_store4(X, row, EPT * q + 4, e[4], e[5], e[6], e[7]);
+        pn_xq_store4(X, row, PN_EPT * q, e[0], e[1], e[2], e[3]);
+        pn_xq_store4(X, row, PN_EPT * q + 4, e[4], e[5], e[6], e[7]);
         // two dims = 12 consecutive columns (a multiple of four from column 32 + 48 q on): three 4-column stores
 #pragma unroll
         for (int i = 0; i < 8; i += 2) {
-            const int col = PN_F + (EPT * q + i) * 6;
+            const int col = PN_F + (PN_EPT * q + i) * 6;
             float s0[3], c0[3], s1[3], c1[3];
             pn_pe_octaves<3>(e[i], s0, c0);
             pn_pe_octaves<3>(e[i + 1], s1, c1);
@@ -617,22 +579,15 @@ __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char
             pn_xq_store4(X, row, col + 8, s1[1], c1[1], s1[2], c1[2]);
         }
     } else {
-    if (HR) { pn_xt_store4(X, row, EPT * q, e[0], e[1], e[2], e[3]); pn_xt_store4(X, row, EPT * q + 4, e[4], e[5], e[6], e[7]); }
-    else { pn_x_store4<false>(X, row, EPT * q, e[0], e[1], e[2], e[3]); pn_x_store4<false>(X, row, EPT * q + 4, e[4], e[5], e[6], e[7]); }
+    pn_xt_store4(X, row, PN_EPT * q, e[0], e[1], e[2], e[3]); pn_xt_store4(X, row, PN_EPT * q + 4, e[4], e[5], e[6], e[7]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int dd = EPT * q + i;
+        const int dd = PN_EPT * q + i;
         float s[3], c[3];
         pn_pe_octaves<3>(e[i], s, c);
-        if (HR) {
-            pn_xt_store2(X, row, PN_F + dd * 6, s[0], c[0]);
-            pn_xt_store2(X, row, PN_F + dd * 6 + 2, s[1], c[1]);
-            pn_xt_store2(X, row, PN_F + dd * 6 + 4, s[2], c[2]);
-        } else {
-            pn_x_store2(X, row, PN_F + dd * 6, s[0], c[0]);
-            pn_x_store2(X, row, PN_F + dd * 6 + 2, s[1], c[1]);
-            pn_x_store2(X, row, PN_F + dd * 6 + 4, s[2], c[2]);
-        }
+        pn_xt_store2(X, row, PN_F + dd * 6, s[0], c[0]);
+        pn_xt_store2(X, row, PN_F + dd * 6 + 2, s[1], c[1]);
+        pn_xt_store2(X, row, PN_F + dd * 6 + 4, s[2], c[2]);
     }
     }
     // PE5 of distance components q and q + 4
@@ -645,15 +600,11 @@ __device__ __forceinline__ void f_build(const FwdArgs &a, const FGather &G, char
 #pragma unroll
             for (int f = 0; f < 5; ++f) {
                 if (MIX) pn_xa_store2(X, row, PN_F * 7 + (comp * 5 + f) * 2, s[f], c[f]);
-                else if (HR) pn_xt_store2(X, row, PN_F * 7 + (comp * 5 + f) * 2, s[f], c[f]);
-                else pn_x_store2(X, row, PN_F * 7 + (comp * 5 + f) * 2, s[f], c[f]);
+                else pn_xt_store2(X, row, PN_F * 7 + (comp * 5 + f) * 2, s[f], c[f]);
             }
         }
     }
-    if (q == 3) {
-        if (MIX || HR) pn_xt_store4(X, row, PN_ONES1, 1.f, 0.f, 0.f, 0.f);
-        else pn_x_store4<false>(X, row, PN_ONES1, 1.f, 0.f, 0.f, 0.f);
-    }
+    if (q == 3) pn_xt_store4(X, row, PN_ONES1, 1.f, 0.f, 0.f, 0.f);
     float fvx = 0.f, fvy = 0.f, fvz = 0.f, fqx = 0.f, fqy = 0.f, fqz = 0.f;
     if (FRAMES) {          // components q of the rotated view and point directions -> thread 0 of the row (lanes l, l + 1, l + 2 hold q = 0, 1, 2)
         fvx = G.rx * G.gx + G.ry * G.gy + G.rz * G.gz;
@@ -728,25 +679,6 @@ __device__ __forceinline__ void f_epilogue(const f32x16 (&acc)[PN_NFB][2], char 
 __device__ __forceinline__ void f_store_masks(unsigned *__restrict__ lmask, long long gtile, int layer, int wave, int lane, const unsigned (&mw)[PN_NFB]) {
 #pragma unroll
     for (int fb = 0; fb < PN_NFB; ++fb) lmask[((gtile * 3 + layer) * 8 + PN_NFB * wave + fb) * 64 + lane] = mw[fb];
-}
-
-__device__ __forceinline__ void f_acc_zero(f32x16 (&acc)[PN_NFB][2]) {
-#pragma unroll
-    for (int i = 0; i < PN_NFB; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-}
-
-// softplus(x) = log(1 + e^x) (raw2out_density, networks.py:262-267) on the hardware exponential / logarithm: absolute error <= 2e-7 for
-// x <= 20 (log of 1 + e^x, e^x >= 0: the argument is >= 1, v_log_f32 / v_exp_f32 are good to an ulp), the identity above
-__device__ __forceinline__ float pn_softplus(float x) {
-#ifdef PN_EMU
-    return x > 20.f ? x : log1pf(expf(x));
-#else
-    return x > 20.f ? x : __logf(1.0f + __expf(x));
-#endif
 }
 
 // ---- the tile's tail in ONE pass over the h4 tile, for K in {1, 2, 4, 8} (the rows of a sample then never straddle a thread's 8 rows):
@@ -840,9 +772,11 @@ template <bool TRAIN, bool PERS, int NP, bool WG2 = false, bool FRAMES = false>
 __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename FwdArgsOf<FRAMES>::type a) {
     constexpr bool MIX = NP == 4;
     static_assert(!FRAMES || (!TRAIN && NP == 3), "per-point frames: the default inference arithmetic only");
-    constexpr bool HR = !MIX;                       // f16x3 tiles with h rounded to nearest (inference and training alike: the same bits); training: h-only copy-outs
+    // Store forms of the tile: the feature build and the epilogues of layers 1-3 write "nearest" planes (MIX: the mixed format; else f16x3 planes with
+    // h rounded to nearest, HR: inference and training alike, the same bits); the layer-4 epilogue writes f16x3.h's classic split (f_epilogue<false>),
+    // which is what f_tail and the backward's h4 read
+    constexpr bool HR = !MIX;
     constexpr bool HC = TRAIN && !WG2;              // the k-major copy-outs read the h plane alone
-    constexpr int NPC = MIX ? 3 : NP;          // (what the classic templates are instantiated with where MIX compiles them away)
     static_assert(!(MIX && WG2), "the two-plane weight-gradient mode keeps f16x3.h's arithmetic everywhere");
     pn_mode_saturate();
     extern __shared__ __attribute__((aligned(16))) char smem_f[];
@@ -875,7 +809,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
     int si0, si1, si2, p0, p1;
     FGather G;
     {
-        const int row = tid0 / TPR, q = tid0 % TPR, k = row - pn_row_div(row, kinv) * K;
+        const int row = tid0 / PN_TPR, q = tid0 % PN_TPR, k = row - pn_row_div(row, kinv) * K;
         si0 = f_sample_of(a, tile, row, Ns, kinv); si1 = tile + stride < tile_last ? f_sample_of(a, tile + stride, row, Ns, kinv) : -1;
         si2 = tile + 2 * stride < tile_last ? f_sample_of(a, tile + 2 * stride, row, Ns, kinv) : -1;
         p0 = si0 >= 0 ? a.pidx[(long long)si0 * a.Kstride + k] : -1;
@@ -892,19 +826,17 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int row = tid / TPR, q = tid % TPR, k = row - pn_row_div(row, kinv) * K;
+        const int row = tid / PN_TPR, q = tid % PN_TPR, k = row - pn_row_div(row, kinv) * K;
         const long long gtile = tb + tile;               // tile index inside the saved area
         PN_LDS_BARRIER();                                 // the previous tile's readers are done with X and the row arrays
         PN_TR(pn_trace_fwd, 0); PN_TR_HWID(pn_trace_fwd);
-        f_build<PERS, MIX, HR, FRAMES>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
+        f_build<PERS, MIX, FRAMES>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
         // Round 4: what the next GEMM needs from GLOBAL memory -- its bias (the accumulators' initial value) and its first weight-fragment
         // chunks -- is requested in front of the barrier that precedes it, not behind: neither depends on LDS, and the L2 round trip
         // (0.6 .. 1.1 us per layer in profiles/r03_phase_trace.json: the "acc = bias" phases) passes under the barrier wait.
         f_acc_bias(P + PO_B1, wave, lane, acc);
-        PnGemmW<18, 8, PN_NFB, PN_WPF, NPC> W1;
-        PnMixW<PN_MIX_NS, 2, 8, PN_NFB> M1;
-        if constexpr (MIX) M1.prefetch(img + PKM_F1, PN_NFB * wave, lane);
-        else W1.prefetch(reinterpret_cast<const uint4 *>(img + PKH_F1), PN_NFB * wave, lane);
+        PnTileW<MIX, 2, 8, NP> W1;
+        W1.prefetch(img, PKH_F1, PKM_F1, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         if (q == 0) {      // weights of the row: normalise over the K slots, multiply by the clamped confidence (:801-811)
             const int ls = pn_row_div(row, kinv);
@@ -926,8 +858,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         // behind 20 stores waits for their acknowledgements from HBM before its first weight fragment counts as arrived (round 2 order:
         // every GEMM phase carried 1 .. 3 us of that).  Behind the GEMM the stores have the epilogue and two barriers to drain.
         PN_TR(pn_trace_fwd, 2);
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 2, 8, PN_NFB>(X, M1, lane, acc);
-        else pn_gemm_f16x3_run<18, 8, PN_NFB, PN_WPF, NPC>(X, W1, lane, acc);
+        W1.run(X, lane, acc);
         if (TRAIN) {           // (behind the GEMM: see above)
             if (HC) {         // the tile's h plane IS the nearest f16: the k-major plane is its transpose
                 if (a.save_x0) pn_copy_out_kmajor_h<PN_NF1>(X, a.sv.x0k, gtile * 8, tid);
@@ -941,16 +872,13 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         f_epilogue<TRAIN, MIX, HR>(acc, X, wave, lane, mask);
         if (TRAIN) f_store_masks(a.sv.lmask, gtile, 0, wave, lane, mask);
         f_acc_bias(P + PO_B2, wave, lane, acc);
-        PnGemmW<16, 8, PN_NFB, PN_WPF, NPC> W2;
-        PnMixW<PN_MIX_NS, 0, 8, PN_NFB> M2;
-        if constexpr (MIX) M2.prefetch(img + PKM_F2, PN_NFB * wave, lane);
-        else W2.prefetch(reinterpret_cast<const uint4 *>(img + PKH_F2), PN_NFB * wave, lane);
+        PnTileW<MIX, 0, 8, NP> W2;
+        W2.prefetch(img, PKH_F2, PKM_F2, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 4);
         // ---- layer 2: 256 -> 256
         PN_TR(pn_trace_fwd, 5);
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M2, lane, acc);
-        else pn_gemm_f16x3_run<16, 8, PN_NFB, PN_WPF, NPC>(X, W2, lane, acc);
+        W2.run(X, lane, acc);
         if (TRAIN) {      // (behind the GEMM: see below)
             if (HC) pn_copy_out_kmajor_h<PN_H>(X, a.sv.h1k, gtile * 8, tid);
             else pn_copy_out_kmajor<PN_H, WG2>(X, a.sv.h1k, gtile * 8, tid, a.sv.h1m);
@@ -961,29 +889,19 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         if (TRAIN) f_store_masks(a.sv.lmask, gtile, 1, wave, lane, mask);
         if (tid < PN_TILE) {     // the row's extras next to h2: columns 256..262, the ones column, zeros up to 271
             const float4 u = *reinterpret_cast<const float4 *>(exb + tid * 8), v = *reinterpret_cast<const float4 *>(exb + tid * 8 + 4);
-            if (MIX || HR) {
-                pn_xt_store4(X, tid, PN_H, u.x, u.y, u.z, u.w);
-                pn_xt_store4(X, tid, PN_H + 4, v.x, v.y, v.z, v.w);
-                pn_xt_store4(X, tid, PN_H + 8, 0.f, 0.f, 0.f, 0.f);
-                pn_xt_store4(X, tid, PN_H + 12, 0.f, 0.f, 0.f, 0.f);
-            } else {
-                pn_x_store4<false>(X, tid, PN_H, u.x, u.y, u.z, u.w);
-                pn_x_store4<false>(X, tid, PN_H + 4, v.x, v.y, v.z, v.w);
-                pn_x_store4<false>(X, tid, PN_H + 8, 0.f, 0.f, 0.f, 0.f);
-                pn_x_store4<false>(X, tid, PN_H + 12, 0.f, 0.f, 0.f, 0.f);
-            }
+            pn_xt_store4(X, tid, PN_H, u.x, u.y, u.z, u.w);
+            pn_xt_store4(X, tid, PN_H + 4, v.x, v.y, v.z, v.w);
+            pn_xt_store4(X, tid, PN_H + 8, 0.f, 0.f, 0.f, 0.f);
+            pn_xt_store4(X, tid, PN_H + 12, 0.f, 0.f, 0.f, 0.f);
         }
         f_acc_bias(P + PO_B3, wave, lane, acc);
-        PnGemmW<17, 8, PN_NFB, PN_WPF, NPC> W3;
-        PnMixW<PN_MIX_NS, 1, 8, PN_NFB> M3;
-        if constexpr (MIX) M3.prefetch(img + PKM_F3, PN_NFB * wave, lane);
-        else W3.prefetch(reinterpret_cast<const uint4 *>(img + PKH_F3), PN_NFB * wave, lane);
+        PnTileW<MIX, 1, 8, NP> W3;
+        W3.prefetch(img, PKH_F3, PKM_F3, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 7);
         // ---- layer 3: 256 + 7 -> 256
         PN_TR(pn_trace_fwd, 8);
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 1, 8, PN_NFB>(X, M3, lane, acc);
-        else pn_gemm_f16x3_run<17, 8, PN_NFB, PN_WPF, NPC>(X, W3, lane, acc);
+        W3.run(X, lane, acc);
         if (TRAIN) {      // (behind the GEMM: see below)
             if (HC) pn_copy_out_kmajor_h<PN_NF1>(X, a.sv.h2k, gtile * 8, tid);
             else pn_copy_out_kmajor<PN_NF1, WG2>(X, a.sv.h2k, gtile * 8, tid, a.sv.h2m);
@@ -993,16 +911,13 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         f_epilogue<TRAIN, MIX, HR>(acc, X, wave, lane, mask);
         if (TRAIN) f_store_masks(a.sv.lmask, gtile, 2, wave, lane, mask);
         f_acc_bias(P + PO_B4, wave, lane, acc);
-        PnGemmW<16, 8, PN_NFB, PN_WPF, NPC> W4;
-        PnMixW<PN_MIX_NS, 0, 8, PN_NFB> M4;
-        if constexpr (MIX) M4.prefetch(img + PKM_F4, PN_NFB * wave, lane);
-        else W4.prefetch(reinterpret_cast<const uint4 *>(img + PKH_F4), PN_NFB * wave, lane);
+        PnTileW<MIX, 0, 8, NP> W4;
+        W4.prefetch(img, PKH_F4, PKM_F4, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 10);
         // ---- layer 4: 256 -> 256
         PN_TR(pn_trace_fwd, 11);
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M4, lane, acc);
-        else pn_gemm_f16x3_run<16, 8, PN_NFB, PN_WPF, NPC>(X, W4, lane, acc);
+        W4.run(X, lane, acc);
         if (TRAIN) {
             if (HC) pn_copy_out_kmajor_h<PN_H>(X, a.sv.h3k, gtile * 8, tid);
             else pn_copy_out_kmajor<PN_H, WG2>(X, a.sv.h3k, gtile * 8, tid, a.sv.h3m);
@@ -1010,8 +925,6 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         PN_TR(pn_trace_fwd, 12);
         // the next tile's point data and the indices of the two after it: requested here, consumed at the top of the next
         // iteration -- their HBM latency passes under the element-wise tail of this tile (nothing of this tile waits for memory any more)
-        const float cf_cur = G.cf;
-        (void)cf_cur;
         const int si_next = si1, p_next = p1;
         if (tile + stride < tile_last) f_gather<PERS, FRAMES>(a, G, si1, p1, q, frames);
         const int p2 = si2 >= 0 ? a.pidx[(long long)si2 * a.Kstride + k] : -1;
@@ -1107,12 +1020,6 @@ __device__ __forceinline__ unsigned c_epilogue(const f32x16 (&acc)[2][2], const 
         }
     return mw;
 }
-__device__ __forceinline__ void c_acc_zero(f32x16 (&acc)[2][2]) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][j][r] = 0.f;
-}
 
 // FRAMES: the view direction is rotated by the frame of the sample's slot-0 point (a.frames) instead of cam.rw2c
 template <bool TRAIN, int NP, bool WG2 = false, bool FRAMES = false>
@@ -1177,7 +1084,7 @@ __global__ __launch_bounds__(256, 2) void k_color_forward(typename FwdArgsOf<FRA
         float4 bias[4];
         // ---- layer 1: 280 (288) -> 128.  Training: every layer's input tile leaves k-major for the weight-gradient GEMM
         if (TRAIN) pn_copy_out_kmajor<PN_NF1, WG2>(X, a.sv.xck, tile * 8, tid, a.sv.xcm);
-        c_acc_zero(acc);
+        pn_acc_zero(acc);
         pn_gemm_f16x3_run<18, 4, 1, 7, NP>(X, WC1, lane, acc);
         c_load_bias(P + PO_BC1, wave, lane, bias);
         PN_LDS_BARRIER();                                 // every wave is done reading the input tile
@@ -1188,7 +1095,7 @@ __global__ __launch_bounds__(256, 2) void k_color_forward(typename FwdArgsOf<FRA
         PN_LDS_BARRIER();
         // ---- layer 2
         if (TRAIN) pn_copy_out_kmajor<PN_HC, WG2>(X, a.sv.c1k, tile * 8, tid, a.sv.c1m);
-        c_acc_zero(acc);
+        pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 7, NP>(X, WC2, lane, acc);
         c_load_bias(P + PO_BC2, wave, lane, bias);
         PN_LDS_BARRIER();
@@ -1199,7 +1106,7 @@ __global__ __launch_bounds__(256, 2) void k_color_forward(typename FwdArgsOf<FRA
         PN_LDS_BARRIER();
         // ---- layer 3
         if (TRAIN) pn_copy_out_kmajor<PN_HC, WG2>(X, a.sv.c2k, tile * 8, tid, a.sv.c2m);
-        c_acc_zero(acc);
+        pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 7, NP>(X, WC3, lane, acc);
         c_load_bias(P + PO_BC3, wave, lane, bias);
         PN_LDS_BARRIER();
@@ -1227,56 +1134,41 @@ __global__ __launch_bounds__(256, 2) void k_color_forward(typename FwdArgsOf<FRA
 }
 }  // namespace
 
-// products per multiply-add of the INFERENCE forward (training always runs three): see f16x3.h NP and include/pnerf.h
-static int pn_inference_products = 3;
-extern "C" int pnerf_set_inference_products(int n) {
-    if (n != 2 && n != 3) return PNERF_E_INVAL;
-    const int old = pn_inference_products;
-    pn_inference_products = n;
-    return old;
-}
-
-// planes per operand of the weight-gradient GEMMs (include/pnerf.h: pnerf_set_wgrad_planes)
-static int pn_wgrad_planes_ = 1;
-int pn_wgrad_planes() { return pn_wgrad_planes_; }
-extern "C" int pnerf_set_wgrad_planes(int n) {
-    if (n != 1 && n != 2) return PNERF_E_INVAL;
-    const int old = pn_wgrad_planes_;
-    pn_wgrad_planes_ = n;
-    return old;
-}
-
-// e4m3 cross terms (mixq.h; 8: the default) or f16 cross terms (16: f16x3.h's three f16 products, the round-2..5 arithmetic) in the aggregator's
-// tile GEMMs, forward and input-gradient chain (include/pnerf.h: pnerf_set_cross_terms)
-static int pn_cross_terms_ = 8;
-int pn_cross_terms() { return pn_cross_terms_; }
-extern "C" int pnerf_set_cross_terms(int bits) {
-    if (bits != 8 && bits != 16) return PNERF_E_INVAL;
-    const int old = pn_cross_terms_;
-    pn_cross_terms_ = bits;
-    return old;
-}
-// which tile kernels run the mixed format when the cross terms are e4m3 (include/pnerf.h: pnerf_set_cross_terms_where): bit 0 = inference
-// forward, bit 1 = training forward, bit 2 = backward (the input-gradient chain).  Default 4: the forward keeps f16 cross terms -- with e4m3 ones
-// its sigma / RGB are 1e-5 .. 6e-5 from the fp32 oracle instead of 1e-6 (inside the 1e-4 bar), but pre-activations within that distance of zero
-// take the other LeakyReLU branch than the oracle's, and the gradient tests against the oracle see those flips (profiles/r06_cross_terms_ab.json)
+// ------------------------------------------------------------------------------ arithmetic settings (include/pnerf.h: pnerf_set_*)
+// One record, process-wide.  products: per multiply-add of the INFERENCE forward (training always runs three; f16x3.h NP).  wgrad_planes: per
+// operand of the weight-gradient GEMMs.  cross_terms: 8 = e4m3 (mixq.h; the default) or 16 = f16 (f16x3.h's three f16 products, the round-2..5
+// arithmetic) in the aggregator's tile GEMMs, forward and input-gradient chain.  mix_where: which tile kernels run the mixed format when the cross
+// terms are e4m3, bit 0 = inference forward, bit 1 = training forward, bit 2 = backward (the input-gradient chain).  Default 4: the forward keeps
+// f16 cross terms -- with e4m3 ones its sigma / RGB are 1e-5 .. 6e-5 from the fp32 oracle instead of 1e-6 (inside the 1e-4 bar), but
+// pre-activations within that distance of zero take the other LeakyReLU branch than the oracle's, and the gradient tests against the oracle see
+// those flips (profiles/r06_cross_terms_ab.json)
 #ifndef PN_MIX_DEFAULT_MASK
 #define PN_MIX_DEFAULT_MASK 4
 #endif
-static int pn_mix_mask_ = -1;
-int pn_mix_mask() {
-    if (pn_mix_mask_ < 0) {
+static PnArith &pn_arith_record() {
+    static PnArith a = [] {
         const char *e = getenv("PNERF_MIX_MASK");          // (dev A/B)
-        pn_mix_mask_ = e ? atoi(e) & 7 : PN_MIX_DEFAULT_MASK;
-    }
-    return pn_cross_terms_ == 8 ? pn_mix_mask_ : 0;
+        return PnArith{3, 1, 8, e ? atoi(e) & 7 : PN_MIX_DEFAULT_MASK};
+    }();
+    return a;
 }
-extern "C" int pnerf_set_cross_terms_where(int mask) {
-    if (mask < 0 || mask > 7) return PNERF_E_INVAL;
-    (void)pn_mix_mask();
-    const int old = pn_mix_mask_;
-    pn_mix_mask_ = mask;
+PnArith pn_arith() { return pn_arith_record(); }
+// every setter: the previous value, or PNERF_E_INVAL (< 0) and nothing changed
+static int pn_arith_set(int PnArith::*field, int v, bool valid) {
+    if (!valid) return PNERF_E_INVAL;
+    const int old = pn_arith_record().*field;
+    pn_arith_record().*field = v;
     return old;
+}
+extern "C" int pnerf_set_inference_products(int n) { return pn_arith_set(&PnArith::products, n, n == 2 || n == 3); }
+extern "C" int pnerf_set_wgrad_planes(int n) { return pn_arith_set(&PnArith::wgrad_planes, n, n == 1 || n == 2); }
+extern "C" int pnerf_set_cross_terms(int bits) { return pn_arith_set(&PnArith::cross_terms, bits, bits == 8 || bits == 16); }
+extern "C" int pnerf_set_cross_terms_where(int mask) { return pn_arith_set(&PnArith::mix_where, mask, mask >= 0 && mask <= 7); }
+extern "C" int pnerf_get_arithmetic(int32_t out[4]) {
+    if (!out) return PNERF_E_INVAL;
+    const PnArith a = pn_arith();
+    out[0] = a.products; out[1] = a.wgrad_planes; out[2] = a.cross_terms; out[3] = a.mix_where;
+    return 0;
 }
 
 // shared with render.hip
@@ -1286,6 +1178,7 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
                           const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K,
                           float *d_decoded, float *d_weight, const PnSaved &sv, long long cap_samples, bool train, bool save_x0,
                           hipStream_t s) {
+    const PnArith ar = pn_arith();                     // one snapshot: every selection below reads it
     FwdArgs a;
     const bool wg2 = train && sv.wg2;                  // two-plane weight-gradient mode: residual planes, X0 saved whole
     if (wg2) save_x0 = true;
@@ -1306,8 +1199,8 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     const int grid_c = (int)(ctiles < 2 * ncu ? (ctiles > 0 ? ctiles : 1) : 2 * ncu);       // two workgroups per CU
     const size_t lds_a = FL_BYTES, lds_c = CL_BYTES;
     const bool pers = d_xyz_pers != nullptr;
-    const bool np2 = !train && pn_inference_products == 2;      // inference with the weights' high plane only (f16x3.h: NP)
-    const bool mix = !wg2 && !np2 && (pn_mix_mask() & (train ? 2 : 1));      // mixq.h: f16 h.h + e4m3 cross terms
+    const bool np2 = !train && ar.products == 2;      // inference with the weights' high plane only (f16x3.h: NP)
+    const bool mix = !wg2 && !np2 && (ar.mix_mask() & (train ? 2 : 1));      // mixq.h: f16 h.h + e4m3 cross terms
     if (frames && (np2 || mix)) return PNERF_E_UNSUP;     // the FRAMES instances exist for the default inference arithmetic only
     // the one place that names the kernel instances: the selection serves both the LDS attribute and the launch
     using FwdKernel = void (*)(FwdArgs);

@@ -47,11 +47,6 @@ struct BwdXArgs : BwdArgs {
 template <bool XYZG> struct BwdArgsOf { using T = BwdArgs; };
 template <> struct BwdArgsOf<true> { using T = BwdXArgs; };
 
-__device__ __forceinline__ void rot3b(const float *M, float x, float y, float z, bool transpose, float &ox, float &oy, float &oz) {
-    if (!transpose) { ox = x * M[0] + y * M[3] + z * M[6]; oy = x * M[1] + y * M[4] + z * M[7]; oz = x * M[2] + y * M[5] + z * M[8]; }
-    else { ox = x * M[0] + y * M[1] + z * M[2]; oy = x * M[3] + y * M[4] + z * M[5]; oz = x * M[6] + y * M[7] + z * M[8]; }
-}
-
 // ------------------------------------------------------------------------------ gradient scale
 // bits of max |d decoded| over the valid samples -> sv.gscale[0] (zeroed by the launcher); every consumer derives the same
 // power of two from it: S = 2^(4 - floor(log2 max)), so that the largest scaled gradient lies in [16, 32)
@@ -96,14 +91,6 @@ constexpr int CB_XRS = 2 * PN_HC + 16, CB_XPL = PN_CTILE * CB_XRS, CB_XBYTES = 2
 constexpr int CB_DRAW = CB_XBYTES, CB_GACC = CB_DRAW + PN_CTILE * 4 * 4, CB_W4 = CB_GACC + 6 * PN_HC * 4, CB_BYTES = CB_W4 + 3 * PN_HC * 4;
 static_assert(3 * CB_BYTES <= 160 * 1024, "three colour workgroups must fit the 160 KB LDS");
 
-__device__ __forceinline__ void cb_acc_zero(f32x16 (&acc)[2][2]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-}
 // d(pre-activation) = acc * LeakyReLU' (sign bits of the forward's pre-activations, same lane -> element map): two planes
 // (saturating, high plane rounded to nearest) into the tile
 __device__ __forceinline__ void cb_epilogue(const f32x16 (&acc)[2][2], unsigned mw, char *X, int wave, int lane) {
@@ -232,7 +219,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X, a.sv.dc3k, tile * 8, tid);
         if (WG2) pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X + CB_XPL, a.sv.dc3m, tile * 8, tid);
         const unsigned mw2 = a.sv.cmask[(tile * 2 + 1) * 256 + tid], mw1 = a.sv.cmask[(tile * 2 + 0) * 256 + tid];
-        cb_acc_zero(acc);
+        pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 4, 3, CB_XRS, CB_XPL>(X, WD3, lane, acc);
         row_values(si_next);                              // (the next tile's six values: consumed at the top of the next iteration)
         si_cur = si_next;
@@ -245,7 +232,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         // ---- d c1 = (d c2 @ Wc2) * lrelu'(c1)
         pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X, a.sv.dc2k, tile * 8, tid);
         if (WG2) pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X + CB_XPL, a.sv.dc2m, tile * 8, tid);
-        cb_acc_zero(acc);
+        pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 4, 3, CB_XRS, CB_XPL>(X, WD2, lane, acc);
         PN_LDS_BARRIER();
         cb_epilogue(acc, mw1, X, wave, lane);
@@ -256,7 +243,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X, a.sv.dc1k, tile * 8, tid);
         if (WG2) pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X + CB_XPL, a.sv.dc1m, tile * 8, tid);
         // ---- d f = d c1 @ Wc1[:, :256]
-        cb_acc_zero(acc);
+        pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 8, 2, 1, 3, CB_XRS, CB_XPL>(X, WD1, lane, acc);
 #pragma unroll
         for (int fb = 0; fb < 2; ++fb)
@@ -293,8 +280,6 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
 //   -> layer-3 extras (d colour, d dir) as a ninth feature block, K split over the four waves
 //   -> d X0 (224 columns: the embedding and its encoding) as fp32 in LDS -> PE chain rule -> atomics into the touched points.
 // Bias gradients are not formed here: they are the ones-column of the weight-gradient GEMMs.
-constexpr int TPR = PN_TPR;                    // threads per tile row in the row-wise phases
-constexpr int EPT = PN_F / TPR;                // embedding dims per thread
 constexpr int BL_ROW = PN_XBYTES, BL_W5 = BL_ROW + 7 * PN_TILE * 4, BL_BYTES = BL_W5 + PN_H * 4;
 constexpr int LDDX = 228;                      // fp32 row stride of the d X0 tile (over the activation tile's space)
 static_assert(2 * BL_BYTES <= 160 * 1024, "two backward workgroups must fit the 160 KB LDS");
@@ -304,19 +289,6 @@ constexpr int LDDX_X = 292, BL_GW = BL_BYTES, BL_BYTES_X = BL_GW + PN_TILE * 4;
 static_assert(2 * BL_BYTES_X <= 160 * 1024, "two xyz_grad backward workgroups must fit the 160 KB LDS");
 static_assert(PN_TILE * LDDX_X * 4 <= PN_XBYTES, "d X0 tile (xyz_grad)");
 
-template <int N> __device__ __forceinline__ float group_sum_b(float v) {
-#pragma unroll
-    for (int off = 1; off < N; off <<= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-template <int AF> __device__ __forceinline__ void b_acc_zero(f32x16 (&acc)[AF][2]) {
-#pragma unroll
-    for (int i = 0; i < AF; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-}
 // dgrad epilogue: accumulators x LeakyReLU' (sign bit of the forward's word of the feature block: element e = (rb * 4 + g) * 4 + i at bit
 // 31 - e) -> both planes of the next dY tile
 template <bool MIX = false>
@@ -347,20 +319,6 @@ __device__ __forceinline__ void b_epilogue(const f32x16 (&acc)[PN_NFB][2], const
 #else
 #define PN_WAVE_LDS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #endif
-__device__ __forceinline__ float pn_softplus_b(float x) {
-#ifdef PN_EMU
-    return x > 20.f ? x : log1pf(expf(x));
-#else
-    return x > 20.f ? x : __logf(1.0f + __expf(x));
-#endif
-}
-__device__ __forceinline__ float pn_sigmoid_b(float x) {
-#ifdef PN_EMU
-    return x > 20.f ? 1.f : 1.0f / (1.0f + expf(-x));
-#else
-    return x > 20.f ? 1.f : __builtin_amdgcn_rcpf(1.0f + __expf(-x));
-#endif
-}
 
 // ---- the tile's front in ONE pass over the h4 tile, for K in {1, 2, 4, 8} (the forward's f_tail mapping: thread -> columns
 // 8 (tid & 31) .. + 7 of rows 8 (tid >> 5) .. + 7, i.e. whole samples): alpha-head backward (d f . h4 per row by the transposing butterfly,
@@ -418,7 +376,7 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
             float dr = 0.f, gw = 0.f;
             if (sidx[r] >= 0) {
                 const float x = xrow[r], dotf = pd[0] * S;
-                const float alpha = pn_softplus_b(x), sg = pn_sigmoid_b(x);
+                const float alpha = pn_softplus(x), sg = pn_sigmoid(x);
                 const int rp = prow[r];
                 // w = wn * clamp(conf) with a straight-through clamp (gradiant_clamp, point_aggregators.py:722-724)
                 if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * invS + (a.zo_gs ? PnZeroOne(zo_conf, a.zo_eps).grad(a.zo_gs[0]) : 0.f));
@@ -483,9 +441,9 @@ __device__ __forceinline__ void b_xyz_row(const BwdXArgs &a, const float *dxr, c
         const float lx = a.sample_loc[si * 3], ly = a.sample_loc[si * 3 + 1], lz = a.sample_loc[si * 3 + 2];
         dwx = px - lx; dwy = py - ly; dwz = pz - lz;
         float pcx, pcy, pcz, scx, scy, scz, d0, d1, d2;
-        rot3b(a.cam.camrot, px - a.cam.campos[0], py - a.cam.campos[1], pz - a.cam.campos[2], false, pcx, pcy, pcz);
-        rot3b(a.cam.camrot, lx - a.cam.campos[0], ly - a.cam.campos[1], lz - a.cam.campos[2], false, scx, scy, scz);
-        rot3b(a.cam.rw2c, dwx, dwy, dwz, true, d0, d1, d2);
+        rot3(a.cam.camrot, px - a.cam.campos[0], py - a.cam.campos[1], pz - a.cam.campos[2], false, pcx, pcy, pcz);
+        rot3(a.cam.camrot, lx - a.cam.campos[0], ly - a.cam.campos[1], lz - a.cam.campos[2], false, scx, scy, scz);
+        rot3(a.cam.rw2c, dwx, dwy, dwz, true, d0, d1, d2);
         const float d3 = (pcx / pcz) * pcz - (scx / scz) * scz, d4 = (pcy / pcz) * pcz - (scy / scz) * scz, d5 = pcz - scz;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -508,12 +466,12 @@ __device__ __forceinline__ void b_xyz_row(const BwdXArgs &a, const float *dxr, c
         for (int k = q; k < K; k += 4) t += gwf[k0 + k] * wrow[k0 + k];
     }
 #pragma unroll
-    for (int i = 0; i < 6; ++i) u[i] = group_sum_b<4>(u[i]);
-    t = group_sum_b<4>(t);
+    for (int i = 0; i < 6; ++i) u[i] = group_sum<4>(u[i]);
+    t = group_sum<4>(t);
     if (rp >= 0 && q < 3) {
         float gx, gy, gz, hx, hy, hz;
-        rot3b(a.cam.rw2c, u[0], u[1], u[2], false, gx, gy, gz);
-        rot3b(a.cam.camrot, u[3], u[4], u[5], true, hx, hy, hz);
+        rot3(a.cam.rw2c, u[0], u[1], u[2], false, gx, gy, gz);
+        rot3(a.cam.camrot, u[3], u[4], u[5], true, hx, hy, hz);
         const float len = sqrtf(dwx * dwx + dwy * dwy + dwz * dwz);
         const float cw = len >= 1e-6f ? -(gwf[row] * wrow[row] - t * wnrm[row]) / (len * len) : 0.f;
         const float v = q == 0 ? gx + hx + cw * dwx : q == 1 ? gy + hy + cw * dwy : gz + hz + cw * dwz;
@@ -570,7 +528,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         int tid = threadIdx.x;                          // (recomputed per tile: see the forward)
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-        const int row = tid / TPR, q = tid % TPR;          // the row-wise phases: 4 threads per tile row
+        const int row = tid / PN_TPR, q = tid % PN_TPR;          // the row-wise phases: 4 threads per tile row
         const long long gtile = tb + tile;
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 0); PN_TR_HWID(pn_trace_bwd);
@@ -630,7 +588,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         const int rp = prow[row];
         float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0;       // the row's embedding values (for its gradient at the end of the tile)
         if (rp >= 0) {
-            const float *ep = a.emb + (long long)rp * PN_F + EPT * q;
+            const float *ep = a.emb + (long long)rp * PN_F + PN_EPT * q;
             e0 = *reinterpret_cast<const float4 *>(ep); e1 = *reinterpret_cast<const float4 *>(ep + 4);
         }
         {
@@ -643,31 +601,26 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             PN_TR(pn_trace_bwd, 2);
         }
         // (round 4: the first weight-fragment chunks of every GEMM are requested in FRONT of the barrier that precedes it -- see the forward)
-        PnGemmW<16, 8, PN_NFB> W4;
-        PnMixW<PN_MIX_NS, 0, 8, PN_NFB> M4;
-        if constexpr (MIX) M4.prefetch(img + PKM_D4, PN_NFB * wave, lane);
-        else W4.prefetch(reinterpret_cast<const uint4 *>(img + PKH_D4), PN_NFB * wave, lane);
+        PnTileW<MIX, 0, 8> W4;
+        W4.prefetch(img, PKH_D4, PKM_D4, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 3);
         // ---- layer 4: dY4 -> d h3
         // (every dY tile is copied out BEHIND its GEMM: stores and loads of a wave share one in-order vmcnt queue, see the forward)
-        b_acc_zero(acc);
+        pn_acc_zero(acc);
         PN_TR(pn_trace_bwd, 4);
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M4, lane, acc);
-        else pn_gemm_f16x3_run<16, 8, PN_NFB>(X, W4, lane, acc);
+        W4.run(X, lane, acc);
         pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy4k, gtile * 8, tid);
         if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy4m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 5);
         b_epilogue<MIX>(acc, m3, X, wave, lane);
-        PnGemmW<16, 9, PN_NFB> W3;
-        PnMixW<PN_MIX_NS, 0, 9, PN_NFB> M3;
-        if constexpr (MIX) M3.prefetch(img + PKM_D3, PN_NFB * wave, lane);
-        else W3.prefetch(reinterpret_cast<const uint4 *>(img + PKH_D3), PN_NFB * wave, lane);
+        PnTileW<MIX, 0, 9> W3;
+        W3.prefetch(img, PKH_D3, PKM_D3, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 6);
         // ---- layer 3: dY3 -> d h2, and the extras block (input columns 256..262 of W3), K split over the waves
-        b_acc_zero(acc);
+        pn_acc_zero(acc);
         PN_TR(pn_trace_bwd, 7);
         // the extras block first, K split over the four waves; their partial sums go straight to the tile's free bytes (80 per row and
         // plane behind column 255, which no GEMM reads: no barrier needed) -- wave w -> plane w >> 1, 32-byte slot w & 1; a lane holds
@@ -676,7 +629,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         //  register allocation of the whole kernel comes out differently from the build that was measured.  Kept, so that the code stays that build's.)
         if (wave < PN_NW) {
             f32x16 acce[1][2];
-            b_acc_zero(acce);
+            pn_acc_zero(acce);
             // (mixed format: wave w takes superchunk w of the block -- the same K split, four f16 chunks and two e4m3 MFMAs per row block)
             if constexpr (MIX) pn_gemm_mix<1, 0, 9, 1>(X, img + PKM_D3, 8, lane, acce, wave);
             else pn_gemm_f16x3<4, 9, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D3), 8, lane, acce, 4 * wave);
@@ -685,8 +638,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                 *reinterpret_cast<float4 *>(X + (wave >> 1) * PN_XPLANE + (32 * rb + (lane & 31)) * PN_XRS + 512 + (wave & 1) * 32 + (lane >> 5) * 16) =
                     make_float4(acce[0][rb][0], acce[0][rb][1], acce[0][rb][2], acce[0][rb][3]);
         }
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 9, PN_NFB>(X, M3, lane, acc);
-        else pn_gemm_f16x3_run<16, 9, PN_NFB>(X, W3, lane, acc);
+        W3.run(X, lane, acc);
         pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy3k, gtile * 8, tid);
         if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy3m, gtile * 8, tid);
         PN_LDS_BARRIER();
@@ -704,9 +656,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             }
             float vx, vy, vz, gx = 0.f, gy = 0.f, gz = 0.f;
             if (p >= 0) {
-                rot3b(a.cam.rw2c, rdx, rdy, rdz, true, vx, vy, vz);
+                rot3(a.cam.rw2c, rdx, rdy, rdz, true, vx, vy, vz);
                 // features (q - v, q . v) with q = dir @ Rw2c^T  ->  d q = dex[3:6] + dex[6] * v ; d dir = d q @ Rw2c
-                rot3b(a.cam.rw2c, u.w + v.z * vx, v.x + v.z * vy, v.y + v.z * vz, false, gx, gy, gz);
+                rot3(a.cam.rw2c, u.w + v.z * vx, v.x + v.z * vy, v.y + v.z * vz, false, gx, gy, gz);
             }
             // Round 5: the six values go back into the row's (consumed) extras slots and leave three lanes per point: a point's 12 bytes of
             // d colour / d dir are one or two 32-byte sectors instead of three (every lane of the old form hit its own sector)
@@ -727,19 +679,16 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                 }
             }
         }
-        PnGemmW<16, 8, PN_NFB> W2;
-        PnMixW<PN_MIX_NS, 0, 8, PN_NFB> M2;
-        if constexpr (MIX) M2.prefetch(img + PKM_D2, PN_NFB * wave, lane);
-        else W2.prefetch(reinterpret_cast<const uint4 *>(img + PKH_D2), PN_NFB * wave, lane);
+        PnTileW<MIX, 0, 8> W2;
+        W2.prefetch(img, PKH_D2, PKM_D2, PN_NFB * wave, lane);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 9);
         // ---- layer 2: dY2 -> d h1
         // (Measured and rejected: pulling the next tile's h4 planes / d f rows / sign words into L2 from here with 4-byte LDS-DMA
         //  reads, one per 128-byte line: 16.65 ms against 16.19 ms -- the load phase is not waiting for HBM.)
-        b_acc_zero(acc);
+        pn_acc_zero(acc);
         PN_TR(pn_trace_bwd, 10);
-        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, 0, 8, PN_NFB>(X, M2, lane, acc);
-        else pn_gemm_f16x3_run<16, 8, PN_NFB>(X, W2, lane, acc);
+        W2.run(X, lane, acc);
         pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy2k, gtile * 8, tid);
         if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy2m, gtile * 8, tid);
         PN_LDS_BARRIER();
@@ -748,7 +697,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 12);
         // ---- layer 1: dY1 -> d X0 (columns 0..223; XYZG: 0..287), fp32 into LDS
-        b_acc_zero(acc);
+        pn_acc_zero(acc);
         PN_TR(pn_trace_bwd, 13);
         // XYZG, wave 3: d X0 columns 224 .. 255 into its idle second accumulator block, 256 .. 287 into acx (two passes of one block each:
         // one pass of two would hold a third block of accumulators at once)
@@ -761,7 +710,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                 pn_gemm_mix<PN_MIX_NS, 0, PN_MB_D1, 1>(X, img + PKM_D1, 6, lane, acc);
                 if constexpr (XYZG) {
                     pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 0, lane, acc1);
-                    b_acc_zero(acx);
+                    pn_acc_zero(acx);
                     pn_gemm_mix<PN_MIX_NS, 0, 2, 1>(X, img + PKM_D1T, 1, lane, acx);
                 }
             }
@@ -771,7 +720,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                 pn_gemm_f16x3<16, PN_MB_D1, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1), 6, lane, acc);
                 if constexpr (XYZG) {
                     pn_gemm_f16x3<16, 2, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1T), 0, lane, acc1);
-                    b_acc_zero(acx);
+                    pn_acc_zero(acx);
                     pn_gemm_f16x3<16, 2, 1>(X, reinterpret_cast<const uint4 *>(img + PKH_D1T), 1, lane, acx);
                 }
             }
@@ -815,10 +764,10 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         if (rp >= 0) {
             float *dr_ = dx + row * LDX;
             const float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
-            float go[EPT];
+            float go[PN_EPT];
 #pragma unroll
-            for (int i = 0; i < EPT; ++i) {
-                const int dd = EPT * q + i;
+            for (int i = 0; i < PN_EPT; ++i) {
+                const int dd = PN_EPT * q + i;
                 float s[3], c[3];
                 pn_pe_octaves<3>(e[i], s, c);
                 float g = dr_[dd], fr = 1.f;
@@ -831,7 +780,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                 go[i] = g * invS;
             }
 #pragma unroll
-            for (int i = 0; i < EPT; i += 4) *reinterpret_cast<float4 *>(dr_ + EPT * q + i) = make_float4(go[i], go[i + 1], go[i + 2], go[i + 3]);
+            for (int i = 0; i < PN_EPT; i += 4) *reinterpret_cast<float4 *>(dr_ + PN_EPT * q + i) = make_float4(go[i], go[i + 1], go[i + 2], go[i + 3]);
         }
         PN_WAVE_LDS_SYNC();
         const int r0w = (row & ~15) + (lane >> 5), col = lane & 31;          // the wave's 16 rows, two per instruction
@@ -1382,6 +1331,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
                            const float *d_decoded, const float *d_weight, const float *d_grad_decoded,
                            const PnSaved &sv, long long n_valid, float *d_grad_params, const pnerf_point_grads *pg,
                            float *d_partials, bool x0_saved, hipStream_t s) {
+    const PnArith ar = pn_arith();                     // one snapshot of the arithmetic settings
     BwdArgs a;
     a.cam = *cam; a.params = d_params; a.packed = (const float4 *)d_packed; a.raydir = d_raydir;
     a.pidx = d_sample_pidx; a.valid_list = d_valid_list; a.counters = d_counters;
@@ -1406,7 +1356,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     const size_t lds_c = CB_BYTES, lds_a = xg ? BL_BYTES_X : BL_BYTES;
     const bool wg2 = sv.wg2 != 0;                      // two-plane weight-gradient mode (the forward of this step ran in it: same process-wide setting)
     if (wg2) x0_saved = true;
-    const bool mix = !wg2 && (pn_mix_mask() & 4);      // mixq.h: e4m3 cross terms in the input-gradient chain
+    const bool mix = !wg2 && (ar.mix_mask() & 4);      // mixq.h: e4m3 cross terms in the input-gradient chain
     // the one place that names the kernel instances: these selections serve both the LDS attribute and the launch (the tile kernel's argument
     // struct follows from xg: the pointer types keep kernel and struct paired)
     void (*const kcb)(BwdArgs) = wg2 ? k_color_backward<true> : k_color_backward<false>;

@@ -201,7 +201,7 @@ extern "C" int pnerf_extract_2d(const float *d_cam_xyz, int64_t n_points, const 
         seen[M.view] = true;
     }
     hipStream_t s = (hipStream_t)stream;
-    PnCarver cv(d_ws, ws_bytes);
+    PnCarver cv(d_ws);
     float4 *proj = cv.take<float4>((size_t)n_points * n_views);
     unsigned *zbuf = nullptr;
     if (a.occ) {

@@ -288,6 +288,24 @@ __device__ __forceinline__ void pn_gemm_mix(const char *X, const char *img, int 
     pn_gemm_mix_run<NSR, NT, MB, NFB, LEAD>(X, W, lane, acc, s0);
 }
 
+// ---- the weights of one 256-wide tile GEMM of the aggregator in either arithmetic: 256 + 16 NT input columns, MB feature blocks in the image, the
+// wave's PN_NFB blocks from block fb0 on.  MIX: the mixed image at off_m (PnMixW); else f16x3.h's two-plane image at off_h (PnGemmW with
+// NP products; NP is not looked at when MIX).  The shape is written once per layer: prefetch() in front of the barrier, run() behind it.
+// (fb0 = PN_NFB * wave is formed by the caller: formed in here, the training forward's sign-word address -- which shares that product -- comes
+//  out with its scalar operands in another order.)
+template <bool MIX, int NT, int MB, int NP = 3>
+struct PnTileW {
+    std::conditional_t<MIX, PnMixW<PN_MIX_NS, NT, MB, PN_NFB>, PnGemmW<16 + NT, MB, PN_NFB, PN_WPF, NP>> w;
+    __device__ __forceinline__ void prefetch(const char *img, int off_h, int off_m, int fb0, int lane) {
+        if constexpr (MIX) w.prefetch(img + off_m, fb0, lane);
+        else w.prefetch(reinterpret_cast<const uint4 *>(img + off_h), fb0, lane);
+    }
+    template <int AF> __device__ __forceinline__ void run(const char *X, int lane, f32x16 (&acc)[AF][2]) {
+        if constexpr (MIX) pn_gemm_mix_run<PN_MIX_NS, NT, MB, PN_NFB>(X, w, lane, acc);
+        else pn_gemm_f16x3_run<16 + NT, MB, PN_NFB, PN_WPF, NP>(X, w, lane, acc);
+    }
+};
+
 // the tile's columns C0 .. C0 + 63 of the HIGH plane -> one k-major plane of 64 features (pn_copy_out_kmajor_cols64 without the residual: the mixed
 // tile's h is already the nearest f16)
 template <int C0>

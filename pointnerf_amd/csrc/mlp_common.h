@@ -24,6 +24,7 @@
 #define PN_NFB    2                  // 32-feature blocks per wave in the 256-wide GEMMs
 static_assert(PN_NTHR == 64 * PN_NW && PN_NW == 4 && PN_NW * PN_NFB == 8, "the tile kernels are written for 4 waves x 2 of the 8 feature blocks each");
 #define PN_TPR    (PN_NTHR / PN_TILE)     // threads per tile row in the row-wise phases
+#define PN_EPT    (PN_F / PN_TPR)         // embedding dims per thread of a row (feature build, embedding gradient)
 #define PN_CTILE  64                 // valid samples per colour-MLP tile
 
 // flat parameter vector (state_dict order, torch [out,in] row-major)
@@ -45,6 +46,42 @@ __device__ __forceinline__ float pn_lrelu_grad(float post) { return post > 0.f ?
 
 template <int... I, class F> __device__ __forceinline__ void pn_static_for_impl(std::integer_sequence<int, I...>, F &&f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void pn_static_for(F &&f) { pn_static_for_impl(std::make_integer_sequence<int, N>{}, f); }
+
+// ---- small device helpers of the tile and colour kernels (aggregate.hip, backward.hip)
+// v @ M (transpose = false: out_j = sum_i v_i M[i][j]) or v @ M^T (true: out_j = sum_i v_i M[j][i]), M row-major 3 x 3
+__device__ __forceinline__ void rot3(const float *M, float x, float y, float z, bool transpose, float &ox, float &oy, float &oz) {
+    if (!transpose) { ox = x * M[0] + y * M[3] + z * M[6]; oy = x * M[1] + y * M[4] + z * M[7]; oz = x * M[2] + y * M[5] + z * M[8]; }
+    else { ox = x * M[0] + y * M[1] + z * M[2]; oy = x * M[3] + y * M[4] + z * M[5]; oz = x * M[6] + y * M[7] + z * M[8]; }
+}
+template <int N> __device__ __forceinline__ float group_sum(float v) {      // sum over N adjacent lanes (N = 4 or 8)
+#pragma unroll
+    for (int off = 1; off < N; off <<= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+template <int AF> __device__ __forceinline__ void pn_acc_zero(f32x16 (&acc)[AF][2]) {
+#pragma unroll
+    for (int i = 0; i < AF; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+// softplus(x) = log(1 + e^x) (raw2out_density, networks.py:262-267) on the hardware exponential / logarithm: absolute error <= 2e-7 for
+// x <= 20 (log of 1 + e^x, e^x >= 0: the argument is >= 1, v_log_f32 / v_exp_f32 are good to an ulp), the identity above; and its derivative
+__device__ __forceinline__ float pn_softplus(float x) {
+#ifdef PN_EMU
+    return x > 20.f ? x : log1pf(expf(x));
+#else
+    return x > 20.f ? x : __logf(1.0f + __expf(x));
+#endif
+}
+__device__ __forceinline__ float pn_sigmoid(float x) {
+#ifdef PN_EMU
+    return x > 20.f ? 1.f : 1.0f / (1.0f + expf(-x));
+#else
+    return x > 20.f ? 1.f : __builtin_amdgcn_rcpf(1.0f + __expf(-x));
+#endif
+}
 
 // ---- saved-activation area (training) -------------------------------------------------------
 struct PnSaved {
@@ -78,13 +115,20 @@ struct PnSaved {
 enum : int { PN_NCLS = 3, PN_CI_COUNT = 0, PN_CI_VBASE = 4, PN_CI_TBASE = 8, PN_CI_TILES = 12, PN_CI_CTILES = 13 /* colour tiles of the step */, PN_CI_WORDS = 16 };
 int pn_class_slots(int K, int kc[3]);
 int pn_classify(const PnSaved &sv, const int32_t *d_valid_list, const int32_t *d_counters, const int32_t *d_pidx, int K, long long n_valid, bool train, bool save_x0, hipStream_t s);
-size_t pn_cls_bytes(long long samples);
-void pn_cls_carve(void *base, long long samples, PnSaved &s);
-size_t pn_saved_bytes(long long n_valid, int K, long long *rows_out, long long *samples_out);
-int pn_cross_terms();                   // 8 (default: mixq.h, e4m3 cross terms in the aggregator's tile GEMMs) or 16 (f16x3.h's three f16 products)
-int pn_mix_mask();                      // bit 0 / 1 / 2: the inference forward / training forward / backward tile kernels run the mixed format (0 when the cross terms are f16)
-int pn_wgrad_planes();                  // 1 (default: one f16 plane per weight-gradient operand) or 2 (both operands as two planes, three products)
+// the layout of the saved area (aggregate.hip): one walk serves the byte count (null base) and the pointers; s.rows / s.samples are set either way
+size_t pn_saved_walk(void *base, long long n_valid, int K, PnSaved &s);
+void pn_cls_walk(PnCarver &cv, PnSaved &s);
+size_t pn_saved_bytes(long long n_valid, int K);
 PnSaved pn_saved_carve(void *base, long long n_valid, int K);
+// the process-wide arithmetic settings (aggregate.hip; include/pnerf.h: pnerf_set_* / pnerf_get_arithmetic).  A launcher takes ONE copy.
+struct PnArith {
+    int products;                       // 3 (default) or 2: MFMA products per multiply-add of the inference forward
+    int wgrad_planes;                   // 1 (default: one f16 plane per weight-gradient operand) or 2 (both operands as two planes, three products)
+    int cross_terms;                    // 8 (default: mixq.h, e4m3 cross terms in the aggregator's tile GEMMs) or 16 (f16x3.h's three f16 products)
+    int mix_where;                      // as stored: bit 0 / 1 / 2 = inference forward / training forward / backward
+    int mix_mask() const { return cross_terms == 8 ? mix_where : 0; }       // which tile kernels run the mixed format now
+};
+PnArith pn_arith();
 
 __host__ __device__ inline int pn_tile_samples(int K) { return PN_TILE / K; }
 // row / K for a tile row (row < 64, K <= 64) without an integer division (a runtime division is ~35 instructions, and the tile kernels

@@ -15,16 +15,15 @@
 static inline size_t pn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int pn_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// simple bump carver over a caller-provided workspace
+// simple bump carver over a caller-provided workspace; without a base it only counts (take() returns null, off = the bytes a real one needs)
 struct PnCarver {
-    char *base; size_t off, cap;
-    PnCarver(void *p, size_t c) : base((char *)p), off(0), cap(c) {}
+    char *base; size_t off;
+    explicit PnCarver(void *p) : base((char *)p), off(0) {}
     template <class T> T *take(size_t n) {
-        T *r = (T *)(base + off);
+        T *r = base ? (T *)(base + off) : nullptr;
         off += pn_align(n * sizeof(T));
         return r;
     }
-    bool ok() const { return off <= cap; }
 };
 
 // ---- optional per-kernel timing with HIP events on the launch stream (prof.hip) ----------------

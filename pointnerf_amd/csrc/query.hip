@@ -253,7 +253,7 @@ extern "C" int pnerf_query(const pnerf_grid_params *gp, const void *d_grid_ws, c
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(d_counters, 0, 8 * sizeof(int), s) != hipSuccess) return PNERF_E_LAUNCH;
     if (R == 0) return 0;
-    PnCarver cv(d_query_ws, ws_bytes);
+    PnCarver cv(d_query_ws);
     int *sel_cnt = cv.take<int>(R);
     int *sel_off = cv.take<int>(R + 1);
     int *scan = cv.take<int>(pn_scan_scratch_ints((long long)R * SR));

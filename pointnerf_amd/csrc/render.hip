@@ -438,12 +438,29 @@ extern "C" int pnerf_touched_flags(const int32_t *d_pidx, int64_t n, int32_t n_p
     return 0;
 }
 
+// the inference workspace: [fs | class partition | room for the weight-gradient partials]; training: the caller passes a pnerf_agg_saved_bytes()
+// area instead.  Like pn_saved_walk: counts without a base, hands out sv.fs and the class arrays with one.
+static size_t agg_workspace_walk(void *base, long long n_valid_max, int K, PnSaved &sv) {
+    PnSaved dims;
+    pn_saved_walk(nullptr, n_valid_max, K, dims);
+    sv = PnSaved();
+    sv.rows = dims.rows; sv.samples = dims.samples;      // the row and sample counts of that capacity; everything else null / 0
+    PnCarver cv(base);
+    sv.fs = cv.take<float>((size_t)sv.samples * PN_H);
+    pn_cls_walk(cv, sv);
+    return cv.off + pn_wgrad_partials_bytes();
+}
 extern "C" size_t pnerf_agg_workspace_bytes(int64_t n_valid_max, int K) {
     if (K <= 0 || K > PNERF_MAX_K || n_valid_max < 0) return 0;
-    // inference: only fs lives here; training: the caller passes a pnerf_agg_saved_bytes() area instead.
-    long long rows, samples;
-    pn_saved_bytes(n_valid_max, K, &rows, &samples);
-    return pn_align((size_t)samples * PN_H * sizeof(float)) + pn_cls_bytes(samples) + pn_wgrad_partials_bytes();
+    PnSaved sv;
+    return agg_workspace_walk(nullptr, n_valid_max, K, sv);
+}
+// what a forward works in: the saved area (training) or the inference workspace
+static int forward_area(void *d_saved, void *d_ws, size_t ws_bytes, long long n_valid_max, int K, PnSaved &sv) {
+    if (d_saved) { sv = pn_saved_carve(d_saved, n_valid_max, K); return 0; }
+    if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(n_valid_max, K)) return PNERF_E_WS;
+    agg_workspace_walk(d_ws, n_valid_max, K, sv);
+    return 0;
 }
 
 static int check_common(const pnerf_camera *cam, const pnerf_points *pts, int R, int SR, int K) {
@@ -469,14 +486,7 @@ extern "C" int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points 
     hipStream_t s = (hipStream_t)stream;
     PnSaved sv;
     const bool train = d_saved != nullptr;
-    if (train) sv = pn_saved_carve(d_saved, n_valid_max, K);
-    else {
-        if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(n_valid_max, K)) return PNERF_E_WS;
-        sv = PnSaved();
-        pn_saved_bytes(n_valid_max, K, &sv.rows, &sv.samples);
-        sv.fs = (float *)d_ws;
-        pn_cls_carve((char *)d_ws + pn_align((size_t)sv.samples * PN_H * sizeof(float)), sv.samples, sv);
-    }
+    if ((rc = forward_area(d_saved, d_ws, ws_bytes, n_valid_max, K, sv)) != 0) return rc;
     if (hipMemsetAsync(d_decoded, 0, (size_t)R * SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
     if (hipMemsetAsync(d_weight, 0, (size_t)R * SR * K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
     if (n_valid_max > 0) {
@@ -556,14 +566,7 @@ extern "C" int pnerf_agg_forward(const pnerf_camera *cam, const pnerf_points *pt
     hipStream_t s = (hipStream_t)stream;
     PnSaved sv;
     const bool train = d_saved != nullptr;
-    if (train) sv = pn_saved_carve(d_saved, n_valid_max, K);
-    else {
-        if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(n_valid_max, K)) return PNERF_E_WS;
-        sv = PnSaved();
-        pn_saved_bytes(n_valid_max, K, &sv.rows, &sv.samples);
-        sv.fs = (float *)d_ws;
-        pn_cls_carve((char *)d_ws + pn_align((size_t)sv.samples * PN_H * sizeof(float)), sv.samples, sv);
-    }
+    if ((rc = forward_area(d_saved, d_ws, ws_bytes, n_valid_max, K, sv)) != 0) return rc;
     if (hipMemsetAsync(d_decoded, 0, (size_t)R * SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
     if (hipMemsetAsync(d_weight, 0, (size_t)R * SR * K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
     if (n_valid_max == 0) return 0;

@@ -227,10 +227,7 @@ def frames_table(Rw2c, n_points):
     _need_cuda(Rw2c, "Rw2c")
     if Rw2c.dim() != 3 or tuple(Rw2c.shape) != (int(n_points), 3, 3):
         raise ValueError("pointnerf_amd: per-point Rw2c must be [%d, 3, 3], got %s" % (int(n_points), list(Rw2c.shape)))
-    lib = L.lib()
-    products = lib.pnerf_set_inference_products(3)
-    lib.pnerf_set_inference_products(products)
-    if products != 3:
+    if arithmetic()[0] != 3:
         raise NotImplementedError("pointnerf_amd: per-point Rw2c is not implemented for set_inference_products(2) (pnerf_set_inference_products); "
                                   "set it back to 3")
     if cross_terms_state()[1] & 1:
@@ -558,13 +555,17 @@ def set_cross_terms(bits, where=None):
     return old, oldw
 
 
+def arithmetic():
+    """(inference products, weight-gradient planes, cross-term bits, cross-term mask as stored): the process-wide settings of
+    set_inference_products / set_wgrad_planes / set_cross_terms, read without writing (pnerf_get_arithmetic)."""
+    out = (ctypes.c_int32 * 4)()
+    L.check(L.lib().pnerf_get_arithmetic(out), "pnerf_get_arithmetic")
+    return tuple(int(v) for v in out)
+
+
 def cross_terms_state():
-    """(bits, mask) currently set: see set_cross_terms"""
-    lib = L.lib()
-    bits = lib.pnerf_set_cross_terms(8)
-    lib.pnerf_set_cross_terms(bits)
-    mask = lib.pnerf_set_cross_terms_where(4)
-    lib.pnerf_set_cross_terms_where(mask)
+    """(bits, mask) in effect: see set_cross_terms (the mask counts only while the bits are 8)"""
+    _, _, bits, mask = arithmetic()
     return bits, (mask if bits == 8 else 0)
 
 
