@@ -195,25 +195,40 @@ typedef struct pnerf_point_grads {   /* gradient accumulators (added to, never z
                                       * the distance encoding and the inverse-distance weights of every neighbor row that names the point */
 } pnerf_point_grads;
 
+/* One render step's inputs: what the four entry points below (pnerf_render_forward / _backward, pnerf_agg_forward / _backward) all read.  The
+ * forward and the backward of a step get the same record. */
+typedef struct pnerf_step {
+    const float *raydir;             /* [R,3]     all four */
+    const float *sample_loc;         /* [R,SR,3]  all four: world position of the samples (pnerf_query's d_sample_loc) */
+    const int32_t *sample_pidx;      /* [R,SR,K]  all four: neighbor point indices, -1 padded */
+    const int32_t *sample_nn;        /* [R,SR]    pnerf_render_forward / _backward only (NULL for the pnerf_agg_* pair): valid neighbors per sample */
+    const int32_t *valid_list;       /* all four: ascending list of r*SR+s with nn>0 (the aggregator's work list) */
+    const int32_t *counters;         /* [8]       all four: [0]=#valid samples (len of valid_list) ... as pnerf_query writes them */
+    const float *xyz_pers;           /* [N,3]     read by pnerf_agg_forward only, both or neither: the caller's perspective coordinates */
+    const float *loc_pers;           /* [R,SR,3]  (sampled_xyz_pers, sample_loc); both NULL = project from cam.  Enforced: one without the other, or
+                                      * either one given to pnerf_render_forward / _backward (which project from cam) -> PNERF_E_INVAL */
+    const float *params;             /* all four: the flat MLP parameter vector (pnerf_mlp_layout order) */
+    const void *packed_mlp;          /* all four: its packed image (pnerf_mlp_pack) */
+    int32_t R, SR, K;
+    int64_t n_valid_max;             /* all four: capacity in valid samples (>= counters[0], which the host reads once per call to size its
+                                      * buffers); the backward of a step must get the n_valid_max of its forward */
+} pnerf_step;
+
 /* bytes of saved activations per valid neighbor row / per valid sample (training forward) */
 size_t pnerf_agg_saved_bytes(int64_t n_valid_samples, int K);
 size_t pnerf_agg_workspace_bytes(int64_t n_valid_max, int K);   /* inference scratch for n_valid_max valid samples */
 size_t pnerf_render_backward_workspace_bytes(int R, int SR);
 
-/* Forward: for every valid sample in d_valid_list computes (sigma, r, g, b) into
+/* Forward: for every valid sample in step->valid_list computes (sigma, r, g, b) into
  * d_decoded [R,SR,4] (zero elsewhere), d_weight [R,SR,K] (normalised distance weights, before
  * confidence), then ray-dist + alpha compositing into d_ray_color [R,3], d_opacity [R,SR],
- * d_bg_trans [R], d_blend_w [R,SR].  n_valid_max = capacity in valid samples (>= d_counters[0], which
- * the host reads once per call to size its buffers).  Inference: d_saved == NULL and d_ws holds
+ * d_bg_trans [R], d_blend_w [R,SR].  Inference: d_saved == NULL and d_ws holds
  * pnerf_agg_workspace_bytes(n_valid_max, K).  Training: d_saved holds pnerf_agg_saved_bytes(n_valid_max, K)
  * and keeps the activations needed by pnerf_render_backward (which must get the same n_valid_max). */
-int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp,
-                         const float *d_params, const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                         const int32_t *d_sample_nn, const int32_t *d_valid_list, const int32_t *d_counters,
-                         int R, int SR, int K,
+int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *step,
                          float *d_decoded, float *d_weight, float *d_ray_color, float *d_opacity,
                          float *d_bg_trans, float *d_blend_w,
-                         void *d_saved, int64_t n_valid_max, void *d_ws, size_t ws_bytes, void *stream);
+                         void *d_saved, void *d_ws, size_t ws_bytes, void *stream);
 
 /* Arithmetic of the INFERENCE forward (d_saved == NULL; pnerf_render_forward and pnerf_agg_forward): every fp32 GEMM operand is two f16
  * planes and a multiply-add is 3 MFMA products (default: fp32-class accuracy, sigma / RGB ~1e-6 from an fp32 evaluation) or 2 (the
@@ -253,15 +268,10 @@ int pnerf_get_arithmetic(int32_t out[4]);
 
 /* Backward of pnerf_render_forward for dL/d(ray_color) = d_grad_ray_color [R,3]:
  * accumulates dL/d(MLP params) into d_grad_params (flat, pnerf_mlp_layout order) and
- * dL/d(point tensors) into pg.  n_valid = the n_valid_max given to the forward call;
+ * dL/d(point tensors) into pg.  d_decoded / d_weight: the forward's results;
  * d_ws holds pnerf_render_backward_workspace_bytes(R, SR). */
-int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp,
-                          const float *d_params,
-                          const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                          const int32_t *d_sample_nn, const int32_t *d_valid_list, const int32_t *d_counters,
-                          int R, int SR, int K, int64_t n_valid,
-                          const float *d_decoded, const float *d_weight, const float *d_opacity,
-                          const float *d_grad_ray_color,
+int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *step,
+                          const float *d_decoded, const float *d_weight, const float *d_grad_ray_color,
                           void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
                           void *d_ws, size_t ws_bytes, void *stream);
 
@@ -278,17 +288,11 @@ int pnerf_touched_flags(const int32_t *d_pidx, int64_t n, int32_t n_points, int3
 int pnerf_compact_valid(const int32_t *d_nn, int64_t n, int32_t *d_list, int32_t *d_counters, void *d_ws, size_t ws_bytes, void *stream);
 
 /* PointAggregator.forward (point_aggregators.py:727-814) on its own: -> d_decoded [R,SR,4], d_weight [R,SR,K].
- * d_xyz_pers [N,3] / d_loc_pers [R,SR,3]: the caller's perspective coordinates (sampled_xyz_pers, sample_loc); both
- * NULL = project from cam.  Scratch/saved sizing as pnerf_render_forward. */
-int pnerf_agg_forward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp, const float *d_params,
-                      const float *d_raydir, const float *d_sample_loc, const float *d_xyz_pers, const float *d_loc_pers,
-                      const int32_t *d_sample_pidx, const int32_t *d_valid_list, const int32_t *d_counters,
-                      int R, int SR, int K, float *d_decoded, float *d_weight,
-                      void *d_saved, int64_t n_valid_max, void *d_ws, size_t ws_bytes, void *stream);
+ * Scratch/saved sizing as pnerf_render_forward. */
+int pnerf_agg_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *step, float *d_decoded, float *d_weight,
+                      void *d_saved, void *d_ws, size_t ws_bytes, void *stream);
 /* its backward for dL/d(decoded) = d_grad_decoded [R,SR,4]; d_ws holds pnerf_render_backward_workspace_bytes(0, 1) */
-int pnerf_agg_backward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp, const float *d_params,
-                       const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                       const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K, int64_t n_valid,
+int pnerf_agg_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *step,
                        const float *d_decoded, const float *d_weight, const float *d_grad_decoded,
                        void *d_saved, float *d_grad_params, const pnerf_point_grads *pg, void *d_ws, size_t ws_bytes, void *stream);
 

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
+ABI_VERSION = 1001                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
@@ -58,6 +59,14 @@ class PointGrads(ctypes.Structure):
                 ("zero_one_gscale", c_void_p), ("zero_one_eps", c_f32), ("xyz", c_void_p)]
 
 
+class Step(ctypes.Structure):
+    _fields_ = [("raydir", c_void_p), ("sample_loc", c_void_p), ("sample_pidx", c_void_p), ("sample_nn", c_void_p), ("valid_list", c_void_p),
+                ("counters", c_void_p), ("xyz_pers", c_void_p), ("loc_pers", c_void_p), ("params", c_void_p), ("packed_mlp", c_void_p),
+                ("R", ctypes.c_int32), ("SR", ctypes.c_int32), ("K", ctypes.c_int32), ("n_valid_max", ctypes.c_int64)]
+
+
+# the head of the four render entry points: (cam, pts, step, ...)
+_STEP_ARGS = [ctypes.POINTER(Camera), ctypes.POINTER(Points), ctypes.POINTER(Step)]
 # symbol -> (restype, argtypes); kept in lock-step with include/pnerf.h (tests/test_boundary.py checks it)
 PROTOTYPES = {
     "pnerf_version": (c_int, []),
@@ -94,11 +103,8 @@ PROTOTYPES = {
     "pnerf_agg_saved_bytes": (c_size_t, [c_i64, c_int]),
     "pnerf_agg_workspace_bytes": (c_size_t, [c_i64, c_int]),
     "pnerf_render_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "pnerf_render_forward": (c_int, [ctypes.POINTER(Camera), ctypes.POINTER(Points), c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_int, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_i64, c_void_p, c_size_t, c_void_p]),
+    # (cam, pts, step, decoded, weight, ray_color, opacity, bg_trans, blend_w, saved, ws, ws_bytes, stream)
+    "pnerf_render_forward": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnerf_set_inference_products": (c_int, [c_int]),
     "pnerf_set_wgrad_planes": (c_int, [c_int]),
     "pnerf_set_cross_terms": (c_int, [c_int]),
@@ -107,13 +113,10 @@ PROTOTYPES = {
     "pnerf_compact_workspace_bytes": (c_size_t, [c_i64]),
     "pnerf_touched_flags": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "pnerf_compact_valid": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "pnerf_agg_forward": (c_int, [ctypes.POINTER(Camera), ctypes.POINTER(Points), c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_size_t, c_void_p]),
-    "pnerf_agg_backward": (c_int, [ctypes.POINTER(Camera), ctypes.POINTER(Points), c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_i64,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(PointGrads),
-                                   c_void_p, c_size_t, c_void_p]),
+    # (cam, pts, step, decoded, weight, saved, ws, ws_bytes, stream)
+    "pnerf_agg_forward": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # (cam, pts, step, decoded, weight, grad_decoded, saved, grad_params, pg, ws, ws_bytes, stream)
+    "pnerf_agg_backward": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(PointGrads), c_void_p, c_size_t, c_void_p]),
     "pnerf_raymarch_forward": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_f32), c_int, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_raymarch_backward": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_f32), c_int, c_int,
@@ -134,15 +137,27 @@ PROTOTYPES = {
     "pnerf_prof_kernel_count": (c_int, []),
     "pnerf_prof_kernel_name": (ctypes.c_char_p, [c_int]),
     "pnerf_prof_collect": (c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)]),
-    "pnerf_render_backward": (c_int, [ctypes.POINTER(Camera), ctypes.POINTER(Points), c_void_p, c_void_p,
-                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_int, c_int, c_int, c_i64,
-                                      c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p, c_void_p, ctypes.POINTER(PointGrads),
-                                      c_void_p, c_size_t, c_void_p]),
+    # (cam, pts, step, decoded, weight, grad_ray_color, saved, grad_params, pg, ws, ws_bytes, stream)
+    "pnerf_render_backward": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(PointGrads), c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None
+
+
+def bind(handle, path):
+    """Give every function of a loaded library (libpnerf_hip.so, or the tests' host emulator of the same C ABI) its prototype; refuses a
+    library that lacks a symbol or was built from another version of include/pnerf.h (same names, other argument lists)."""
+    for name, (res, args) in PROTOTYPES.items():
+        try:
+            fn = getattr(handle, name)
+        except AttributeError as e:
+            raise RuntimeError("pointnerf_amd: %s lacks symbol %s (stale build?)" % (os.path.basename(path), name)) from e
+        fn.restype, fn.argtypes = res, args
+    got = handle.pnerf_version()
+    if got != ABI_VERSION:
+        raise RuntimeError("pointnerf_amd: %s reports pnerf_version() %d, this binding is written for %d (stale build?)"
+                           % (os.path.basename(path), got, ABI_VERSION))
+    return handle
 
 
 def lib():
@@ -153,14 +168,7 @@ def lib():
             raise RuntimeError(
                 "pointnerf_amd: %s not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback for this path." % LIB_PATH)
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
-            try:
-                fn = getattr(handle, name)
-            except AttributeError as e:
-                raise RuntimeError("pointnerf_amd: libpnerf_hip.so lacks symbol %s (stale build?)" % name) from e
-            fn.restype, fn.argtypes = res, args
-        _lib = handle
+        _lib = bind(ctypes.CDLL(LIB_PATH), LIB_PATH)
     return _lib
 
 

@@ -1172,12 +1172,10 @@ extern "C" int pnerf_get_arithmetic(int32_t out[4]) {
 }
 
 // shared with render.hip
-int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, const float *d_params, const void *d_packed,
-                          const float *d_raydir, const float *d_sample_loc, const float *d_xyz_pers, const float *d_loc_pers,
-                          const int32_t *d_sample_pidx,
-                          const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K,
-                          float *d_decoded, float *d_weight, const PnSaved &sv, long long cap_samples, bool train, bool save_x0,
-                          hipStream_t s) {
+int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step &st, float *d_decoded, float *d_weight,
+                          const PnSaved &sv, bool train, bool save_x0, hipStream_t s) {
+    const int K = st.K;
+    const long long cap_samples = st.n_valid_max;
     const PnArith ar = pn_arith();                     // one snapshot: every selection below reads it
     FwdArgs a;
     const bool wg2 = train && sv.wg2;                  // two-plane weight-gradient mode: residual planes, X0 saved whole
@@ -1185,20 +1183,18 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     a.save_x0 = save_x0 ? 1 : 0;
     a.cam = *cam;
     a.xyz = pts->xyz; a.emb = pts->embedding; a.conf = pts->conf; a.dir = pts->dir; a.color = pts->color;
-    a.params = d_params; a.packed = (const float4 *)d_packed;
-    a.raydir = d_raydir; a.sample_loc = d_sample_loc; a.xyz_pers = d_xyz_pers; a.loc_pers = d_loc_pers; a.pidx = d_sample_pidx; a.valid_list = d_valid_list; a.counters = d_counters;
-    a.R = R; a.SR = SR; a.K = K; a.TS = pn_tile_samples(K);
+    a.params = st.params; a.packed = (const float4 *)st.packed_mlp;
+    a.raydir = st.raydir; a.sample_loc = st.sample_loc; a.xyz_pers = st.xyz_pers; a.loc_pers = st.loc_pers; a.pidx = st.sample_pidx; a.valid_list = st.valid_list; a.counters = st.counters;
+    a.R = st.R; a.SR = st.SR; a.K = K; a.TS = pn_tile_samples(K);
     a.cap_samples = cap_samples;
     a.decoded = d_decoded; a.weight = d_weight; a.sv = sv;
     const bool frames = pts->frames != nullptr;
     if (frames && train) return PNERF_E_INVAL;            // per-point frames are render-only (include/pnerf.h: pnerf_points.frames)
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 256;
-    const long long ctiles = (cap_samples + PN_CTILE - 1) / PN_CTILE;
-    const int grid_c = (int)(ctiles < 2 * ncu ? (ctiles > 0 ? ctiles : 1) : 2 * ncu);       // two workgroups per CU
+    const int ncu = pn_cu_count();
+    if (!ncu) return PNERF_E_LAUNCH;
+    const int grid_c = pn_capped_grid((cap_samples + PN_CTILE - 1) / PN_CTILE, 2LL * ncu);       // two workgroups per CU
     const size_t lds_a = FL_BYTES, lds_c = CL_BYTES;
-    const bool pers = d_xyz_pers != nullptr;
+    const bool pers = st.xyz_pers != nullptr;
     const bool np2 = !train && ar.products == 2;      // inference with the weights' high plane only (f16x3.h: NP)
     const bool mix = !wg2 && !np2 && (ar.mix_mask() & (train ? 2 : 1));      // mixq.h: f16 h.h + e4m3 cross terms
     if (frames && (np2 || mix)) return PNERF_E_UNSUP;     // the FRAMES instances exist for the default inference arithmetic only
@@ -1216,7 +1212,7 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     const FwdKernel cfn = wg2 ? k_color_forward<true, 3, true> : train ? k_color_forward<true, 3> : np2 ? k_color_forward<false, 2> : k_color_forward<false, 3>;
     if (hipFuncSetAttribute(frames ? reinterpret_cast<const void *>(kfnf) : reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a) != hipSuccess) return PNERF_E_LAUNCH;
     if (hipFuncSetAttribute(frames ? reinterpret_cast<const void *>(cfnf) : reinterpret_cast<const void *>(cfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c) != hipSuccess) return PNERF_E_LAUNCH;
-    int rc = pn_classify(sv, d_valid_list, d_counters, d_sample_pidx, K, cap_samples, train, save_x0, s);
+    int rc = pn_classify(sv, st.valid_list, st.counters, st.sample_pidx, K, cap_samples, train, save_x0, s);
     if (rc) return rc;
     a.cls_list = sv.cls_list; a.cls_info = sv.cls_info; a.Kstride = K;
     int kc[PN_NCLS];
@@ -1225,8 +1221,7 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
         PnProfScope prof(PNK_AGG_FWD, s);
         for (int j = 0; j < ncls; ++j) {            // class sizes are only known on the device: the grid covers the worst case, surplus workgroups return at once
             a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
-            const long long tiles = (cap_samples + a.TS - 1) / a.TS;
-            const int grid_a = (int)(tiles < 2LL * ncu ? (tiles > 0 ? tiles : 1) : 2LL * ncu);     // two workgroups per CU
+            const int grid_a = pn_capped_grid((cap_samples + a.TS - 1) / a.TS, 2LL * ncu);     // two workgroups per CU
             if (frames) { FwdArgsF af; static_cast<FwdArgs &>(af) = a; af.frames = pts->frames; hipLaunchKernelGGL(kfnf, dim3(grid_a), dim3(PN_NTHR), lds_a, s, af); }
             else hipLaunchKernelGGL(kfn, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
         }

@@ -1325,17 +1325,16 @@ __global__ void k_zero_one_empty(const float *__restrict__ conf, const int *__re
 }
 }  // namespace
 
-int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, const float *d_params, const void *d_packed,
-                           const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                           const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K,
-                           const float *d_decoded, const float *d_weight, const float *d_grad_decoded,
-                           const PnSaved &sv, long long n_valid, float *d_grad_params, const pnerf_point_grads *pg,
+int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step &st, const float *d_decoded, const float *d_weight,
+                           const float *d_grad_decoded, const PnSaved &sv, float *d_grad_params, const pnerf_point_grads *pg,
                            float *d_partials, bool x0_saved, hipStream_t s) {
+    const int K = st.K;
+    const long long n_valid = st.n_valid_max;
     const PnArith ar = pn_arith();                     // one snapshot of the arithmetic settings
     BwdArgs a;
-    a.cam = *cam; a.params = d_params; a.packed = (const float4 *)d_packed; a.raydir = d_raydir;
-    a.pidx = d_sample_pidx; a.valid_list = d_valid_list; a.counters = d_counters;
-    a.SR = SR; a.K = K; a.TS = pn_tile_samples(K); a.cap_samples = n_valid;
+    a.cam = *cam; a.params = st.params; a.packed = (const float4 *)st.packed_mlp; a.raydir = st.raydir;
+    a.pidx = st.sample_pidx; a.valid_list = st.valid_list; a.counters = st.counters;
+    a.SR = st.SR; a.K = K; a.TS = pn_tile_samples(K); a.cap_samples = n_valid;
     a.decoded = d_decoded; a.weight = d_weight; a.grad_decoded = d_grad_decoded; a.sv = sv;
     a.emb = pts->embedding;
     a.gparams = d_grad_params; a.g_emb = pg->embedding; a.g_conf = pg->conf; a.g_dir = pg->dir; a.g_color = pg->color;
@@ -1344,15 +1343,13 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     if (!a.g_emb || !a.g_conf || !a.g_dir || !a.g_color) return PNERF_E_INVAL;
     // xyz_grad: the fused render path (world-coordinate distances recomputed from xyz / sample_loc)
     BwdXArgs ax;
-    ax.xyz = pts->xyz; ax.sample_loc = d_sample_loc; ax.g_xyz = pg->xyz;
+    ax.xyz = pts->xyz; ax.sample_loc = st.sample_loc; ax.g_xyz = pg->xyz;
     const bool xg = ax.g_xyz != nullptr;
     if (xg && x0_saved) return PNERF_E_UNSUP;
     if (xg && (!ax.xyz || !ax.sample_loc)) return PNERF_E_INVAL;
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu = 256;
-    const long long ctiles = (n_valid + PN_CTILE - 1) / PN_CTILE;
-    const int grid_c = (int)(ctiles < 3 * ncu ? (ctiles > 0 ? ctiles : 1) : 3 * ncu);       // 40 KB of LDS: three workgroups per CU
+    const int ncu = pn_cu_count();
+    if (!ncu) return PNERF_E_LAUNCH;
+    const int grid_c = pn_capped_grid((n_valid + PN_CTILE - 1) / PN_CTILE, 3LL * ncu);       // 40 KB of LDS: three workgroups per CU
     const size_t lds_c = CB_BYTES, lds_a = xg ? BL_BYTES_X : BL_BYTES;
     const bool wg2 = sv.wg2 != 0;                      // two-plane weight-gradient mode (the forward of this step ran in it: same process-wide setting)
     if (wg2) x0_saved = true;
@@ -1368,11 +1365,8 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     a.cls_list = sv.cls_list; a.cls_info = sv.cls_info; a.valid_list = sv.cls_list;
     // the scale of this call's gradients (a power of two derived on the device from max |d decoded| over the valid samples)
     if (hipMemsetAsync(sv.gscale, 0, 4 * sizeof(unsigned), s) != hipSuccess) return PNERF_E_LAUNCH;
-    {
-        const long long blocks = (n_valid + 255) / 256;
-        hipLaunchKernelGGL(k_grad_max, dim3((unsigned)(blocks < 1024 ? (blocks > 0 ? blocks : 1) : 1024)), dim3(256), 0, s, sv.cls_list, d_counters, (long long)n_valid, d_grad_decoded, sv.gscale);
-    }
-    if (a.zo_gs) hipLaunchKernelGGL(k_zero_one_empty, dim3(1), dim3(1), 0, s, a.conf, d_counters, (long long)SR * K, a.zo_gs, a.zo_eps, a.g_conf);
+    hipLaunchKernelGGL(k_grad_max, dim3(pn_capped_grid((n_valid + 255) / 256, 1024)), dim3(256), 0, s, sv.cls_list, st.counters, n_valid, d_grad_decoded, sv.gscale);
+    if (a.zo_gs) hipLaunchKernelGGL(k_zero_one_empty, dim3(1), dim3(1), 0, s, a.conf, st.counters, (long long)st.SR * K, a.zo_gs, a.zo_eps, a.g_conf);
     { PnProfScope prof(PNK_COLOR_BWD, s);
       hipLaunchKernelGGL(kcb, dim3(grid_c), dim3(256), lds_c, s, a); }
     int kc[PN_NCLS];
@@ -1380,8 +1374,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     { PnProfScope prof(PNK_AGG_BWD, s);
       for (int j = 0; j < ncls; ++j) {
           a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
-          const long long tiles = (n_valid + a.TS - 1) / a.TS;                    // worst-case grid, two workgroups per CU
-          const int grid_a = (int)(tiles < 2LL * ncu ? (tiles > 0 ? tiles : 1) : 2LL * ncu);
+          const int grid_a = pn_capped_grid((n_valid + a.TS - 1) / a.TS, 2LL * ncu);      // worst-case grid, two workgroups per CU
           if (xg) { static_cast<BwdArgs &>(ax) = a; hipLaunchKernelGGL(kax, dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax); }
           else hipLaunchKernelGGL(kab, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
       } }
@@ -1392,7 +1385,6 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     // weight gradients over every tile of every class (+ their zero padding tiles): the tile count lives on the device, the host
     // bound is the allocation.  samples: only the first n_valid rows of fs / pe / c1.. exist -- the GEMM masks the rest of the
     // last colour tile (0 * stale bits could be NaN)
-    (void)R;
     const long long rows = sv.rows, smps = sv.samples;
     const int *dt = sv.cls_info + PN_CI_TILES, *ct = sv.cls_info + PN_CI_CTILES;
     // the four aggregator layers (the bias gradients are the operands' own ones column in layers 1 and 3, the constant-ones tail in layers 2 and

@@ -120,6 +120,14 @@ size_t pn_saved_walk(void *base, long long n_valid, int K, PnSaved &s);
 void pn_cls_walk(PnCarver &cv, PnSaved &s);
 size_t pn_saved_bytes(long long n_valid, int K);
 PnSaved pn_saved_carve(void *base, long long n_valid, int K);
+// the launchers behind the four render entry points (render.hip validates, then calls): the aggregator + colour MLP forward (aggregate.hip)
+// and their backward with the weight-gradient GEMMs (backward.hip; d_partials holds pn_wgrad_partials_bytes())
+int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step &st, float *d_decoded, float *d_weight,
+                          const PnSaved &sv, bool train, bool save_x0, hipStream_t s);
+int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step &st, const float *d_decoded, const float *d_weight,
+                           const float *d_grad_decoded, const PnSaved &sv, float *d_grad_params, const pnerf_point_grads *pg,
+                           float *d_partials, bool x0_saved, hipStream_t s);
+size_t pn_wgrad_partials_bytes();
 // the process-wide arithmetic settings (aggregate.hip; include/pnerf.h: pnerf_set_* / pnerf_get_arithmetic).  A launcher takes ONE copy.
 struct PnArith {
     int products;                       // 3 (default) or 2: MFMA products per multiply-add of the inference forward

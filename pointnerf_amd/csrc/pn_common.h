@@ -15,6 +15,15 @@
 static inline size_t pn_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 static inline int pn_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// a launch grid that covers `tiles` work items with at most `cap` workgroups (never an empty grid); the caps of the tile kernels are
+// workgroups per CU times pn_cu_count(): the CUs of the current device (256 where the attribute cannot be read; 0: no current device)
+static inline int pn_capped_grid(long long tiles, long long cap) { return (int)(tiles < cap ? (tiles > 0 ? tiles : 1) : cap); }
+static inline int pn_cu_count() {
+    int dev = 0, ncu = 256;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    return hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? ncu : 256;
+}
+
 // simple bump carver over a caller-provided workspace; without a base it only counts (take() returns null, off = the bytes a real one needs)
 struct PnCarver {
     char *base; size_t off;

@@ -10,20 +10,6 @@
 // the ones the caller asks for.
 #include "mlp_common.h"
 
-int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, const float *d_params, const void *d_packed,
-                          const float *d_raydir, const float *d_sample_loc, const float *d_xyz_pers, const float *d_loc_pers,
-                          const int32_t *d_sample_pidx,
-                          const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K,
-                          float *d_decoded, float *d_weight, const PnSaved &sv, long long cap_samples, bool train, bool save_x0,
-                          hipStream_t s);
-int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, const float *d_params, const void *d_packed,
-                           const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                           const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K,
-                           const float *d_decoded, const float *d_weight, const float *d_grad_decoded,
-                           const PnSaved &sv, long long n_valid, float *d_grad_params, const pnerf_point_grads *pg,
-                           float *d_partials, bool x0_saved, hipStream_t s);
-size_t pn_wgrad_partials_bytes();
-
 namespace {
 constexpr int TPB = 256;
 
@@ -438,6 +424,21 @@ extern "C" int pnerf_touched_flags(const int32_t *d_pidx, int64_t n, int32_t n_p
     return 0;
 }
 
+// the argument of the two ray-march kernels, in its two forms: ray distances and validity from the camera, the samples' positions and their
+// neighbor counts (the fused path), or supplied by the caller with the background colour (the stand-alone ray_march())
+static RmArgs rm_args(const pnerf_camera &cam, const float *sample_loc, const int32_t *nn, const float *decoded, int R, int SR) {
+    RmArgs ra = {};
+    ra.cam = cam; ra.sample_loc = sample_loc; ra.nn = nn; ra.decoded = decoded; ra.R = R; ra.SR = SR;
+    return ra;
+}
+static RmArgs rm_args(const float *ray_dist, const uint8_t *valid8, const float *bg3_host, const float *decoded, int R, int SR) {
+    RmArgs ra = {};
+    ra.ray_dist = ray_dist; ra.valid8 = valid8; ra.decoded = decoded; ra.R = R; ra.SR = SR;
+    ra.cam.has_bg = bg3_host ? 1 : 0;
+    if (bg3_host) { ra.cam.bg[0] = bg3_host[0]; ra.cam.bg[1] = bg3_host[1]; ra.cam.bg[2] = bg3_host[2]; }
+    return ra;
+}
+
 // the inference workspace: [fs | class partition | room for the weight-gradient partials]; training: the caller passes a pnerf_agg_saved_bytes()
 // area instead.  Like pn_saved_walk: counts without a base, hands out sv.fs and the class arrays with one.
 static size_t agg_workspace_walk(void *base, long long n_valid_max, int K, PnSaved &sv) {
@@ -455,81 +456,72 @@ extern "C" size_t pnerf_agg_workspace_bytes(int64_t n_valid_max, int K) {
     PnSaved sv;
     return agg_workspace_walk(nullptr, n_valid_max, K, sv);
 }
-// what a forward works in: the saved area (training) or the inference workspace
-static int forward_area(void *d_saved, void *d_ws, size_t ws_bytes, long long n_valid_max, int K, PnSaved &sv) {
-    if (d_saved) { sv = pn_saved_carve(d_saved, n_valid_max, K); return 0; }
-    if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(n_valid_max, K)) return PNERF_E_WS;
-    agg_workspace_walk(d_ws, n_valid_max, K, sv);
-    return 0;
-}
 
-static int check_common(const pnerf_camera *cam, const pnerf_points *pts, int R, int SR, int K) {
-    if (!cam || !pts || R < 0 || SR <= 0 || K <= 0 || K > PNERF_MAX_K) return PNERF_E_INVAL;
+// THE validation of the four render entry points, in the order that decides between two codes.  ST_RENDER: the render pair, which reads
+// st->sample_nn and projects from cam (it refuses st->xyz_pers / st->loc_pers; the pnerf_agg_* pair takes both or neither); ST_SAVING: a training
+// forward or a backward (per-point frames are render-only: include/pnerf.h, pnerf_points.frames); call_ptrs: the results or gradients of this
+// call are all there
+enum : unsigned { ST_RENDER = 1, ST_SAVING = 2 };
+static int check_step(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st, unsigned kind, bool call_ptrs) {
+    const bool render = kind & ST_RENDER;
+    if (!cam || !pts || !st || st->R < 0 || st->SR <= 0 || st->K <= 0 || st->K > PNERF_MAX_K) return PNERF_E_INVAL;
     if (pts->feat_dim != PN_F) return PNERF_E_UNSUP;
     if (!pts->xyz || !pts->embedding || !pts->conf || !pts->dir || !pts->color) return PNERF_E_UNSUP;
+    if (!st->packed_mlp || !st->params || !st->raydir || !st->sample_loc || !st->sample_pidx || (render && !st->sample_nn) || !st->valid_list || !st->counters) return PNERF_E_INVAL;
+    if (!call_ptrs) return PNERF_E_INVAL;
+    if (render ? (st->xyz_pers || st->loc_pers) : (st->xyz_pers == nullptr) != (st->loc_pers == nullptr)) return PNERF_E_INVAL;
+    if (pts->frames && (kind & ST_SAVING)) return PNERF_E_INVAL;
     return 0;
 }
 
-extern "C" int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp, const float *d_params,
-                                    const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                                    const int32_t *d_sample_nn, const int32_t *d_valid_list, const int32_t *d_counters,
-                                    int R, int SR, int K,
+// the aggregator + colour MLP of both forwards, after check_step: works in the saved area (training) or in the inference workspace
+static int agg_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step &st, float *d_decoded, float *d_weight,
+                       void *d_saved, void *d_ws, size_t ws_bytes, bool save_x0, hipStream_t s) {
+    if (st.R == 0) return 0;
+    PnSaved sv;
+    if (d_saved) sv = pn_saved_carve(d_saved, st.n_valid_max, st.K);
+    else if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(st.n_valid_max, st.K)) return PNERF_E_WS;
+    else agg_workspace_walk(d_ws, st.n_valid_max, st.K, sv);
+    if (hipMemsetAsync(d_decoded, 0, (size_t)st.R * st.SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipMemsetAsync(d_weight, 0, (size_t)st.R * st.SR * st.K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
+    if (st.n_valid_max == 0) return 0;
+    return pn_agg_forward_launch(cam, pts, st, d_decoded, d_weight, sv, d_saved != nullptr, save_x0, s);
+}
+
+extern "C" int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
                                     float *d_decoded, float *d_weight, float *d_ray_color, float *d_opacity,
                                     float *d_bg_trans, float *d_blend_w,
-                                    void *d_saved, int64_t n_valid_max, void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_common(cam, pts, R, SR, K);
-    if (rc) return rc;
-    if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_sample_nn || !d_valid_list || !d_counters) return PNERF_E_INVAL;
-    if (!d_decoded || !d_weight || !d_ray_color || !d_opacity || !d_bg_trans || !d_blend_w) return PNERF_E_INVAL;
-    if (pts->frames && d_saved) return PNERF_E_INVAL;      // per-point frames are render-only
-    if (R == 0) return 0;
+                                    void *d_saved, void *d_ws, size_t ws_bytes, void *stream) {
+    int rc = check_step(cam, pts, st, ST_RENDER | (d_saved ? ST_SAVING : 0), d_decoded && d_weight && d_ray_color && d_opacity && d_bg_trans && d_blend_w);
+    if (rc || st->R == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
-    PnSaved sv;
-    const bool train = d_saved != nullptr;
-    if ((rc = forward_area(d_saved, d_ws, ws_bytes, n_valid_max, K, sv)) != 0) return rc;
-    if (hipMemsetAsync(d_decoded, 0, (size_t)R * SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipMemsetAsync(d_weight, 0, (size_t)R * SR * K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
-    if (n_valid_max > 0) {
-        rc = pn_agg_forward_launch(cam, pts, d_params, d_packed_mlp, d_raydir, d_sample_loc, nullptr, nullptr, d_sample_pidx, d_valid_list, d_counters,
-                                   R, SR, K, d_decoded, d_weight, sv, n_valid_max, train, /*save_x0=*/false, s);
-        if (rc) return rc;
-    }
-    RmArgs ra;
-    ra.cam = *cam; ra.sample_loc = d_sample_loc; ra.decoded = d_decoded; ra.nn = d_sample_nn; ra.ray_dist = nullptr; ra.valid8 = nullptr; ra.R = R; ra.SR = SR;
+    if ((rc = agg_forward(cam, pts, *st, d_decoded, d_weight, d_saved, d_ws, ws_bytes, /*save_x0=*/false, s)) != 0) return rc;
     { PnProfScope prof(PNK_RAYMARCH_FWD, s);
-    hipLaunchKernelGGL(k_raymarch_forward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, ra, d_ray_color, d_opacity, d_bg_trans, d_blend_w, (float *)nullptr); }
+    hipLaunchKernelGGL(k_raymarch_forward, dim3(pn_cdiv(st->R, TPB / 64)), dim3(TPB), 0, s, rm_args(*cam, st->sample_loc, st->sample_nn, d_decoded, st->R, st->SR),
+                       d_ray_color, d_opacity, d_bg_trans, d_blend_w, (float *)nullptr); }
     PN_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp, const float *d_params,
-                                     const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                                     const int32_t *d_sample_nn, const int32_t *d_valid_list, const int32_t *d_counters,
-                                     int R, int SR, int K, int64_t n_valid,
-                                     const float *d_decoded, const float *d_weight, const float *d_opacity,
-                                     const float *d_grad_ray_color,
+extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
+                                     const float *d_decoded, const float *d_weight, const float *d_grad_ray_color,
                                      void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
                                      void *d_ws, size_t ws_bytes, void *stream) {
-    (void)d_opacity;
-    int rc = check_common(cam, pts, R, SR, K);
+    int rc = check_step(cam, pts, st, ST_RENDER | ST_SAVING, d_decoded && d_weight && d_grad_ray_color && d_saved && d_grad_params && pg && d_ws);
     if (rc) return rc;
-    if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_sample_nn || !d_valid_list || !d_counters) return PNERF_E_INVAL;
-    if (!d_decoded || !d_weight || !d_grad_ray_color || !d_saved || !d_grad_params || !pg || !d_ws) return PNERF_E_INVAL;
-    if (pts->frames) return PNERF_E_INVAL;                 // per-point frames are render-only
+    const int R = st->R, SR = st->SR;
     const size_t gd_bytes = pn_align((size_t)R * SR * 4 * sizeof(float));
     if (ws_bytes < gd_bytes + pn_wgrad_partials_bytes()) return PNERF_E_WS;
-    if (R == 0 || n_valid == 0) return 0;
+    if (R == 0 || st->n_valid_max == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     float *grad_decoded = (float *)d_ws;
     float *partials = (float *)((char *)d_ws + gd_bytes);
-    RmArgs ra;
-    ra.cam = *cam; ra.sample_loc = d_sample_loc; ra.decoded = d_decoded; ra.nn = d_sample_nn; ra.ray_dist = nullptr; ra.valid8 = nullptr; ra.R = R; ra.SR = SR;
     { PnProfScope prof(PNK_RAYMARCH_BWD, s);
-    hipLaunchKernelGGL(k_raymarch_backward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, ra, d_grad_ray_color, grad_decoded); }
+    hipLaunchKernelGGL(k_raymarch_backward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, rm_args(*cam, st->sample_loc, st->sample_nn, d_decoded, R, SR),
+                       d_grad_ray_color, grad_decoded); }
     PN_CHECK_LAUNCH();
-    PnSaved sv = pn_saved_carve(d_saved, n_valid, K);
-    return pn_agg_backward_launch(cam, pts, d_params, d_packed_mlp, d_raydir, d_sample_loc, d_sample_pidx, d_valid_list, d_counters,
-                                  R, SR, K, d_decoded, d_weight, grad_decoded, sv, n_valid, d_grad_params, pg, partials, /*x0_saved=*/false, s);
+    return pn_agg_backward_launch(cam, pts, *st, d_decoded, d_weight, grad_decoded, pn_saved_carve(d_saved, st->n_valid_max, st->K), d_grad_params, pg,
+                                  partials, /*x0_saved=*/false, s);
 }
 
 extern "C" size_t pnerf_render_backward_workspace_bytes(int R, int SR) {
@@ -552,44 +544,21 @@ extern "C" int pnerf_compact_valid(const int32_t *d_nn, int64_t n, int32_t *d_li
     return pn_compact_gt0_i32(d_nn, n, d_list, d_counters, (int *)d_ws, s);
 }
 
-extern "C" int pnerf_agg_forward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp, const float *d_params,
-                                 const float *d_raydir, const float *d_sample_loc, const float *d_xyz_pers, const float *d_loc_pers,
-                                 const int32_t *d_sample_pidx, const int32_t *d_valid_list, const int32_t *d_counters,
-                                 int R, int SR, int K, float *d_decoded, float *d_weight,
-                                 void *d_saved, int64_t n_valid_max, void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_common(cam, pts, R, SR, K);
-    if (rc) return rc;
-    if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_valid_list || !d_counters || !d_decoded || !d_weight) return PNERF_E_INVAL;
-    if ((d_xyz_pers == nullptr) != (d_loc_pers == nullptr)) return PNERF_E_INVAL;
-    if (pts->frames && d_saved) return PNERF_E_INVAL;      // per-point frames are render-only
-    if (R == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    PnSaved sv;
-    const bool train = d_saved != nullptr;
-    if ((rc = forward_area(d_saved, d_ws, ws_bytes, n_valid_max, K, sv)) != 0) return rc;
-    if (hipMemsetAsync(d_decoded, 0, (size_t)R * SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipMemsetAsync(d_weight, 0, (size_t)R * SR * K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
-    if (n_valid_max == 0) return 0;
-    return pn_agg_forward_launch(cam, pts, d_params, d_packed_mlp, d_raydir, d_sample_loc, d_xyz_pers, d_loc_pers, d_sample_pidx,
-                                 d_valid_list, d_counters, R, SR, K, d_decoded, d_weight, sv, n_valid_max, train, /*save_x0=*/train, s);
+extern "C" int pnerf_agg_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st, float *d_decoded, float *d_weight,
+                                 void *d_saved, void *d_ws, size_t ws_bytes, void *stream) {
+    const int rc = check_step(cam, pts, st, d_saved ? ST_SAVING : 0, d_decoded && d_weight);
+    return rc ? rc : agg_forward(cam, pts, *st, d_decoded, d_weight, d_saved, d_ws, ws_bytes, /*save_x0=*/d_saved != nullptr, (hipStream_t)stream);
 }
 
-extern "C" int pnerf_agg_backward(const pnerf_camera *cam, const pnerf_points *pts, const void *d_packed_mlp, const float *d_params,
-                                  const float *d_raydir, const float *d_sample_loc, const int32_t *d_sample_pidx,
-                                  const int32_t *d_valid_list, const int32_t *d_counters, int R, int SR, int K, int64_t n_valid,
+extern "C" int pnerf_agg_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
                                   const float *d_decoded, const float *d_weight, const float *d_grad_decoded,
                                   void *d_saved, float *d_grad_params, const pnerf_point_grads *pg, void *d_ws, size_t ws_bytes, void *stream) {
-    int rc = check_common(cam, pts, R, SR, K);
+    int rc = check_step(cam, pts, st, ST_SAVING, d_decoded && d_weight && d_grad_decoded && d_saved && d_grad_params && pg && d_ws);
     if (rc) return rc;
-    if (!d_packed_mlp || !d_params || !d_raydir || !d_sample_loc || !d_sample_pidx || !d_valid_list || !d_counters) return PNERF_E_INVAL;
-    if (!d_decoded || !d_weight || !d_grad_decoded || !d_saved || !d_grad_params || !pg || !d_ws) return PNERF_E_INVAL;
-    if (pts->frames) return PNERF_E_INVAL;                 // per-point frames are render-only
     if (ws_bytes < pn_wgrad_partials_bytes()) return PNERF_E_WS;
-    if (R == 0 || n_valid == 0) return 0;
-    PnSaved sv = pn_saved_carve(d_saved, n_valid, K);
-    return pn_agg_backward_launch(cam, pts, d_params, d_packed_mlp, d_raydir, d_sample_loc, d_sample_pidx, d_valid_list, d_counters,
-                                  R, SR, K, d_decoded, d_weight, d_grad_decoded, sv, n_valid, d_grad_params, pg, (float *)d_ws,
-                                  /*x0_saved=*/true, (hipStream_t)stream);
+    if (st->R == 0 || st->n_valid_max == 0) return 0;
+    return pn_agg_backward_launch(cam, pts, *st, d_decoded, d_weight, d_grad_decoded, pn_saved_carve(d_saved, st->n_valid_max, st->K), d_grad_params, pg,
+                                  (float *)d_ws, /*x0_saved=*/true, (hipStream_t)stream);
 }
 
 // ray_march(ray_dist, ray_valid, ray_features, radiance, alpha, bg_color)   models/rendering/diff_ray_marching.py:508-554
@@ -598,10 +567,7 @@ extern "C" int pnerf_raymarch_forward(const float *d_ray_dist, const uint8_t *d_
                                       float *d_bg_trans, void *stream) {
     if (!d_ray_dist || !d_ray_valid || !d_features || !d_ray_color || !d_opacity || !d_acc_trans || !d_blend_w || !d_bg_trans || R < 0 || SR <= 0) return PNERF_E_INVAL;
     if (R == 0) return 0;
-    RmArgs ra = {};
-    ra.decoded = d_features; ra.ray_dist = d_ray_dist; ra.valid8 = d_ray_valid; ra.R = R; ra.SR = SR;
-    ra.cam.has_bg = bg3_host ? 1 : 0;
-    if (bg3_host) { ra.cam.bg[0] = bg3_host[0]; ra.cam.bg[1] = bg3_host[1]; ra.cam.bg[2] = bg3_host[2]; }
+    const RmArgs ra = rm_args(d_ray_dist, d_ray_valid, bg3_host, d_features, R, SR);
     hipStream_t s = (hipStream_t)stream;
     PnProfScope prof(PNK_RAYMARCH_FWD, s);
     hipLaunchKernelGGL(k_raymarch_forward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, ra, d_ray_color, d_opacity, d_bg_trans, d_blend_w, d_acc_trans);
@@ -613,10 +579,7 @@ extern "C" int pnerf_raymarch_backward(const float *d_ray_dist, const uint8_t *d
                                        int R, int SR, const float *d_grad_ray_color, float *d_grad_features, void *stream) {
     if (!d_ray_dist || !d_ray_valid || !d_features || !d_grad_ray_color || !d_grad_features || R < 0 || SR <= 0) return PNERF_E_INVAL;
     if (R == 0) return 0;
-    RmArgs ra = {};
-    ra.decoded = d_features; ra.ray_dist = d_ray_dist; ra.valid8 = d_ray_valid; ra.R = R; ra.SR = SR;
-    ra.cam.has_bg = bg3_host ? 1 : 0;
-    if (bg3_host) { ra.cam.bg[0] = bg3_host[0]; ra.cam.bg[1] = bg3_host[1]; ra.cam.bg[2] = bg3_host[2]; }
+    const RmArgs ra = rm_args(d_ray_dist, d_ray_valid, bg3_host, d_features, R, SR);
     hipStream_t s = (hipStream_t)stream;
     PnProfScope prof(PNK_RAYMARCH_BWD, s);
     hipLaunchKernelGGL(k_raymarch_backward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, ra, d_grad_ray_color, d_grad_features);

@@ -8,8 +8,6 @@ replaces the reference's ``neural_points(...) -> aggregator(...) -> ray_dist -> 
 neural_points.py:132; every reference script leaves it 0): the backward then also forms d xyz through the distance encoding and the
 inverse-distance weights (k_agg_backward's XYZG instances), and returns it in the same point-gradient bucket.
 """
-import ctypes
-
 import torch
 
 from . import _lib as L
@@ -58,8 +56,7 @@ class FusedRender(torch.autograd.Function):
         # (the C structure holds raw pointers: keep the arrays it points to alive until the backward has read them)
         ctx.point_arrays = (emb.detach().reshape(-1, emb.shape[-1]), conf.detach().reshape(-1, 1), pdir.detach().reshape(-1, 3),
                             color.detach().reshape(-1, 3))
-        if env.get("frames") is not None and env["train"]:
-            raise NotImplementedError("per-point Rw2c (scene editing) is render-only: no training forward, no backward")
+        ops.frames_are_render_only(env.get("frames"), env["train"])
         pts = ops.make_points(env["xyz"], *ctx.point_arrays, frames=env.get("frames"))
         # a step whose saved activations would exceed the arena budget runs its forward without saving anything; the backward then
         # re-runs the forward chunk of rays by chunk of rays (ops.arena_budget_bytes)
@@ -69,7 +66,7 @@ class FusedRender(torch.autograd.Function):
         # only what the backward reads: ray_color must NOT be kept -- the returned tensor's grad_fn is this node, and node -> fwd -> ray_color ->
         # node is a reference cycle that only Python's cycle collector breaks: a training-mode forward that is never back-propagated (an evaluation
         # under enabled gradients) then holds its activation arena (tens of GB) until some later collection
-        ctx.env, ctx.pts, ctx.fwd = env, pts, {k: fwd[k] for k in ("saved", "decoded", "weight", "opacity")}
+        ctx.env, ctx.pts, ctx.fwd = env, pts, {k: fwd[k] for k in ("saved", "decoded", "weight")}
         env["_saved"] = fwd["saved"]              # (a caller that drops this result without a backward hands the arena block back itself)
         ctx.shapes = (tuple(emb.shape), tuple(conf.shape), tuple(pdir.shape), tuple(color.shape))
         ctx.n_mlp = len(mlp_params)
@@ -81,7 +78,7 @@ class FusedRender(torch.autograd.Function):
         if env["train"] and env.get("zero_one_eps") is not None:
             ctx.zo = float(env["zero_one_eps"])
             zo_sum = ops.zero_one_sum(ctx.point_arrays[1].reshape(-1), env["dense"]["sample_pidx"], env["dense"]["ray_hit"], ctx.zo)
-        # ONE call (a second one replaces the set): every output the backward does not differentiate.  decoded / weight / opacity are kept in
+        # ONE call (a second one replaces the set): every output the backward does not differentiate.  decoded / weight are kept in
         # ctx.fwd -- were they differentiable outputs, node -> ctx.fwd -> tensor -> grad_fn = node would be a reference cycle that holds the
         # activation arena of every training forward that is never back-propagated
         nondiff = [fwd["opacity"], fwd["bg_trans"], fwd["blend_w"], fwd["decoded"], fwd["weight"]]
@@ -200,61 +197,33 @@ class Aggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, env, emb, conf, pdir, color, *mlp_params):
         # env: dict(cam, xyz_slots [N',3], xyz_pers [N',3], loc_w, loc_pers, raydir [R,3], pidx, nn, R, SR, K, flat, packed, train, layout)
-        lib = L.lib()
-        dev = emb.device
-        R, SR, K = env["R"], env["SR"], env["K"]
-        nn = env["nn"]
-        vlist, counters = ops.compact_valid(nn)
+        vlist, counters = ops.compact_valid(env["nn"])
         n_valid = int(counters[0].item())
         # (the C structure holds raw pointers: the per-slot arrays must stay alive until the backward has read them)
         slot_arrays = (emb.detach().reshape(-1, emb.shape[-1]).contiguous(), conf.detach().reshape(-1, 1).contiguous(),
                        pdir.detach().reshape(-1, 3).contiguous(), color.detach().reshape(-1, 3).contiguous())
-        if env.get("frames") is not None and env["train"]:
-            raise NotImplementedError("per-point Rw2c (scene editing) is render-only: no training forward, no backward")
+        ops.frames_are_render_only(env.get("frames"), env["train"])
         pts = ops.make_points(env["xyz_slots"], *slot_arrays, frames=env.get("frames"))
-        f32 = dict(dtype=torch.float32, device=dev)
-        decoded, weight = torch.empty(R, SR, 4, **f32), torch.empty(R, SR, K, **f32)
-        saved = ws = None
-        nw = 0
-        if env["train"]:
-            saved = ops.ARENA.take(lib.pnerf_agg_saved_bytes(n_valid, K), dev)
-        else:
-            nw = lib.pnerf_agg_workspace_bytes(n_valid, K)
-            ws = torch.empty(nw, dtype=torch.uint8, device=dev)
-        L.check(lib.pnerf_agg_forward(ctypes.byref(env["cam"]), ctypes.byref(pts), ops._ptr(env["packed"]), ops._ptr(env["flat"]),
-                                      ops._ptr(env["raydir"]), ops._ptr(env["loc_w"]), ops._ptr(env["xyz_pers"]), ops._ptr(env["loc_pers"]),
-                                      ops._ptr(env["pidx"]), ops._ptr(vlist), ops._ptr(counters), R, SR, K, ops._ptr(decoded), ops._ptr(weight),
-                                      ops._ptr(saved), n_valid, ops._ptr(ws), nw, ops._stream()), "pnerf_agg_forward")
-        ctx.env, ctx.pts, ctx.keep = env, pts, (vlist, counters, saved, decoded, weight, n_valid)
+        st = ops.make_step(env["raydir"], dict(sample_loc=env["loc_w"], sample_pidx=env["pidx"], valid_list=vlist, counters=counters), env["flat"],
+                           env["packed"], env["R"], env["SR"], env["K"], n_valid, xyz_pers=env["xyz_pers"], loc_pers=env["loc_pers"])
+        fwd = ops.agg_forward(env["cam"], pts, st, env["train"])
+        ctx.env, ctx.pts, ctx.keep = env, pts, (st, fwd)
         ctx.slot_arrays = slot_arrays
         ctx.shapes = (tuple(emb.shape), tuple(conf.shape), tuple(pdir.shape), tuple(color.shape))
-        ctx.mark_non_differentiable(weight)
-        return decoded, weight
+        ctx.mark_non_differentiable(fwd["weight"])
+        return fwd["decoded"], fwd["weight"]
 
     @staticmethod
     def backward(ctx, g_decoded, *unused):
-        lib = L.lib()
         env = ctx.env
-        vlist, counters, saved, decoded, weight, n_valid = ctx.keep
-        if saved is None:
+        st, fwd = ctx.keep
+        if fwd["saved"] is None:
             raise RuntimeError("pointnerf_amd: backward through an aggregator call that was run with train=False")
-        dev = g_decoded.device
-        R, SR, K = env["R"], env["SR"], env["K"]
         gflat = torch.zeros_like(env["flat"])
-        names = ("embedding", "conf", "dir", "color")
-        grads = [torch.zeros(shp, dtype=torch.float32, device=dev) for shp in ctx.shapes]
-        pg = L.PointGrads()
-        pg.embedding, pg.conf, pg.dir, pg.color = [g.data_ptr() for g in grads]
-        nws = lib.pnerf_render_backward_workspace_bytes(0, 1)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        gd = g_decoded.reshape(R, SR, 4).contiguous().float()
-        if n_valid > 0:
-            L.check(lib.pnerf_agg_backward(ctypes.byref(env["cam"]), ctypes.byref(ctx.pts), ops._ptr(env["packed"]), ops._ptr(env["flat"]),
-                                           ops._ptr(env["raydir"]), ops._ptr(env["loc_w"]), ops._ptr(env["pidx"]), ops._ptr(vlist),
-                                           ops._ptr(counters), R, SR, K, n_valid, ops._ptr(decoded), ops._ptr(weight), ops._ptr(gd),
-                                           ops._ptr(saved), ops._ptr(gflat), ctypes.byref(pg), ops._ptr(ws), nws, ops._stream()),
-                    "pnerf_agg_backward")
-        ops.ARENA.give(saved)
+        grads = [torch.zeros(shp, dtype=torch.float32, device=g_decoded.device) for shp in ctx.shapes]
+        if st.n_valid_max > 0:
+            ops.agg_backward(env["cam"], ctx.pts, st, fwd, g_decoded, gflat, dict(zip(("points_embeding", "points_conf", "points_dir", "points_color"), grads)))
+        ops.ARENA.give(fwd["saved"])
         ctx.keep = ctx.slot_arrays = None
         gm = tuple(gflat[o:o + n].view(shp) for (o, n, shp) in env["layout"])
         return (None,) + tuple(grads) + gm

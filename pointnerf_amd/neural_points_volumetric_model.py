@@ -75,9 +75,7 @@ class NeuralPointsRayMarching(nn.Module):
         # (pnerf_points.frames) -- it is never read back to the host -- and is render-only, like the reference's frozen Rw2c
         frames = None
         if isinstance(npnt.Rw2c, torch.Tensor) and npnt.Rw2c.dim() == 3:
-            if train:
-                raise NotImplementedError("per-point Rw2c (scene editing) is render-only: run the forward under torch.no_grad() -- the reference "
-                                          "freezes Rw2c and editing never trains" + (" (xyz_grad > 0 included)" if xyz_leaf else ""))
+            ops.frames_are_render_only(npnt.Rw2c, train, " (xyz_grad > 0 included)" if xyz_leaf else "")
             frames = ops.frames_table(npnt.Rw2c, npnt.xyz.shape[0])
         R = raydir.reshape(-1, 3).shape[0]
         if train and self._pool_rays < R:              # worst case (every ray hits): ~16 live [R,SR,K] fp32 tensors around the loss

@@ -61,6 +61,14 @@ def _need_cuda(t, name):
         raise RuntimeError("pointnerf_amd: %s must be a device tensor (this path has no CPU implementation)" % name)
 
 
+def _dense_arg(t, name, dtype, numel=None):
+    _need_cuda(t, name)
+    if t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise ValueError("pointnerf_amd: %s must be a contiguous %s tensor%s, got %s %s"
+                         % (name, dtype, "" if numel is None else " of %d elements" % numel, t.dtype, list(t.shape)))
+    return t
+
+
 # ------------------------------------------------------------------------------------------ grid
 def mid_depths(D, near, far):
     """The D mid-point depths of near_far_linear_ray_generation with jitter=0
@@ -251,6 +259,56 @@ def make_points(xyz, emb, conf, pdir, color, frames=None):
     return p
 
 
+def frames_are_render_only(frames, train, hint=""):
+    """THE refusal of per-point Rw2c frames in a training forward (and so in any backward): pnerf_points.frames is render-only."""
+    if frames is not None and train:
+        raise NotImplementedError("per-point Rw2c (scene editing) is render-only: run the forward under torch.no_grad() -- the reference "
+                                  "freezes Rw2c and editing never trains" + hint)
+
+
+def make_step(raydir, dense, flat, packed, R, SR, K, n_valid, xyz_pers=None, loc_pers=None):
+    """pnerf_step: the inputs the four render entry points share.  ``dense`` = the query's dict (sample_loc, sample_pidx, valid_list, counters and,
+    for the render pair, sample_nn); ``n_valid`` = the capacity in valid samples (>= counters[0]; the same for the forward and the backward of a
+    step); ``xyz_pers`` / ``loc_pers`` (both or neither) for the stand-alone aggregator.  The returned structure keeps the tensors it points into alive."""
+    R, SR, K = int(R), int(SR), int(K)
+    f32, i32 = torch.float32, torch.int32
+    fields = [("raydir", raydir, f32, R * 3), ("sample_loc", dense["sample_loc"], f32, R * SR * 3), ("sample_pidx", dense["sample_pidx"], i32, R * SR * K),
+              ("valid_list", dense["valid_list"], i32, None), ("counters", dense["counters"], i32, 8), ("params", flat, f32, None),
+              ("packed_mlp", packed, torch.uint8, None)]
+    fields += [f for f in (("sample_nn", dense.get("sample_nn"), i32, R * SR), ("xyz_pers", xyz_pers, f32, None), ("loc_pers", loc_pers, f32, R * SR * 3))
+               if f[1] is not None]                     # (half a pair of perspective coordinates: the library's PNERF_E_INVAL)
+    st = L.Step()
+    for name, t, dtype, numel in fields:
+        setattr(st, name, _ptr(_dense_arg(t, name, dtype, numel)))
+    st.R, st.SR, st.K, st.n_valid_max = R, SR, K, int(n_valid)
+    st._keep = [t for _, t, _, _ in fields]
+    return st
+
+
+def _forward_scratch(n_valid, K, train, device):
+    """what a forward works in, (saved, ws, ws_bytes): an arena block of pnerf_agg_saved_bytes (training; handed back with ARENA.give) or a
+    workspace of pnerf_agg_workspace_bytes (inference)"""
+    lib = L.lib()
+    if train:
+        return ARENA.take(lib.pnerf_agg_saved_bytes(n_valid, K), device), None, 0
+    nws = lib.pnerf_agg_workspace_bytes(n_valid, K)
+    return None, torch.empty(nws, dtype=torch.uint8, device=device), nws
+
+
+def _point_grads(grads, ready_event=None, zero_one=None):
+    """pnerf_point_grads over grads = dict(points_embeding, points_conf, points_dir, points_color[, xyz]) (device tensors, added to)"""
+    pg = L.PointGrads()
+    pg.embedding, pg.conf = grads["points_embeding"].data_ptr(), grads["points_conf"].data_ptr()
+    pg.dir, pg.color = grads["points_dir"].data_ptr(), grads["points_color"].data_ptr()
+    if grads.get("xyz") is not None:
+        pg.xyz = grads["xyz"].data_ptr()
+    if zero_one is not None:
+        pg.zero_one_gscale, pg.zero_one_eps = zero_one[0].data_ptr(), float(zero_one[1])
+    if ready_event is not None:          # a torch.cuda.Event that has been recorded once (so that its hipEvent_t exists)
+        pg.ready_event = ready_event.cuda_event
+    return pg
+
+
 class Arena:
     """Grow-only device scratch for the saved activations of one in-flight training forward.  The arena is tens of GB
     at bench size and its exact size changes every step with the number of valid samples; letting torch's caching
@@ -353,23 +411,15 @@ def render_forward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, tra
     """pnerf_render_forward.  n_valid = host copy of dense['counters'][0] (capacity of the scratch).
     Returns dict(decoded, weight, ray_color, opacity, bg_trans, blend_w, saved)."""
     dev = raydir.device
-    lib = L.lib()
     f32 = dict(dtype=torch.float32, device=dev)
     decoded = torch.empty(R, SR, 4, **f32); weight = torch.empty(R, SR, K, **f32)
     ray_color = torch.empty(R, 3, **f32); opacity = torch.empty(R, SR, **f32)
     bg_trans = torch.empty(R, **f32); blend_w = torch.empty(R, SR, **f32)
-    saved = ws = None
-    if train:
-        saved = ARENA.take(lib.pnerf_agg_saved_bytes(n_valid, K), dev)
-        nws = 0
-    else:
-        nws = lib.pnerf_agg_workspace_bytes(n_valid, K)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-    L.check(lib.pnerf_render_forward(ctypes.byref(cam), ctypes.byref(pts), _ptr(packed), _ptr(flat), _ptr(raydir),
-                                     _ptr(dense["sample_loc"]), _ptr(dense["sample_pidx"]), _ptr(dense["sample_nn"]),
-                                     _ptr(dense["valid_list"]), _ptr(dense["counters"]), R, SR, K,
-                                     _ptr(decoded), _ptr(weight), _ptr(ray_color), _ptr(opacity), _ptr(bg_trans), _ptr(blend_w),
-                                     _ptr(saved), n_valid, _ptr(ws), nws, _stream()), "pnerf_render_forward")
+    st = make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
+    saved, ws, nws = _forward_scratch(n_valid, K, train, dev)
+    L.check(L.lib().pnerf_render_forward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st),
+                                         _ptr(decoded), _ptr(weight), _ptr(ray_color), _ptr(opacity), _ptr(bg_trans), _ptr(blend_w),
+                                         _ptr(saved), _ptr(ws), nws, _stream()), "pnerf_render_forward")
     return dict(decoded=decoded, weight=weight, ray_color=ray_color, opacity=opacity, bg_trans=bg_trans,
                 blend_w=blend_w, saved=saved)
 
@@ -381,24 +431,36 @@ def render_backward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, fw
     conf gradient of the zero-one regulariser over the hit rays' neighbor table is added by the same call (pnerf_point_grads.zero_one_gscale;
     ``dense`` must be the query's own output: its counters [1] and [3] count the empty slots)."""
     lib = L.lib()
-    pg = L.PointGrads()
-    pg.embedding, pg.conf = grads["points_embeding"].data_ptr(), grads["points_conf"].data_ptr()
-    pg.dir, pg.color = grads["points_dir"].data_ptr(), grads["points_color"].data_ptr()
-    if grads.get("xyz") is not None:
-        pg.xyz = grads["xyz"].data_ptr()
-    if zero_one is not None:
-        pg.zero_one_gscale, pg.zero_one_eps = zero_one[0].data_ptr(), float(zero_one[1])
-    if ready_event is not None:          # a torch.cuda.Event that has been recorded once (so that its hipEvent_t exists)
-        pg.ready_event = ready_event.cuda_event
+    st = make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
+    pg = _point_grads(grads, ready_event, zero_one)
     nws = lib.pnerf_render_backward_workspace_bytes(R, SR)
     ws = torch.empty(nws, dtype=torch.uint8, device=raydir.device)
     g = grad_ray_color.contiguous().float()
-    L.check(lib.pnerf_render_backward(ctypes.byref(cam), ctypes.byref(pts), _ptr(packed), _ptr(flat), _ptr(raydir),
-                                      _ptr(dense["sample_loc"]), _ptr(dense["sample_pidx"]), _ptr(dense["sample_nn"]),
-                                      _ptr(dense["valid_list"]), _ptr(dense["counters"]), R, SR, K, n_valid,
-                                      _ptr(fwd["decoded"]), _ptr(fwd["weight"]), _ptr(fwd["opacity"]), _ptr(g),
-                                      _ptr(fwd["saved"]), _ptr(grad_flat), ctypes.byref(pg), _ptr(ws), nws, _stream()),
-            "pnerf_render_backward")
+    L.check(lib.pnerf_render_backward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), _ptr(fwd["decoded"]), _ptr(fwd["weight"]), _ptr(g),
+                                      _ptr(fwd["saved"]), _ptr(grad_flat), ctypes.byref(pg), _ptr(ws), nws, _stream()), "pnerf_render_backward")
+
+
+def agg_forward(cam, pts, st, train):
+    """pnerf_agg_forward on ``st`` = make_step(...) of the gathered per-slot arrays (no sample_nn; xyz_pers / loc_pers optional).
+    Returns dict(decoded [R,SR,4], weight [R,SR,K], saved)."""
+    f32 = dict(dtype=torch.float32, device=st._keep[0].device)
+    decoded, weight = torch.empty(st.R, st.SR, 4, **f32), torch.empty(st.R, st.SR, st.K, **f32)
+    saved, ws, nws = _forward_scratch(st.n_valid_max, st.K, train, f32["device"])
+    L.check(L.lib().pnerf_agg_forward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), _ptr(decoded), _ptr(weight),
+                                      _ptr(saved), _ptr(ws), nws, _stream()), "pnerf_agg_forward")
+    return dict(decoded=decoded, weight=weight, saved=saved)
+
+
+def agg_backward(cam, pts, st, fwd, grad_decoded, grad_flat, grads):
+    """pnerf_agg_backward for its forward's ``st`` and result ``fwd``: accumulates into grad_flat (MLP) and the per-slot ``grads`` (the keys of
+    render_backward's)."""
+    lib = L.lib()
+    pg = _point_grads(grads)
+    nws = lib.pnerf_render_backward_workspace_bytes(0, 1)      # (no [R,SR,4] gradient of its own: the weight-gradient partials only)
+    ws = torch.empty(nws, dtype=torch.uint8, device=grad_flat.device)
+    gd = grad_decoded.reshape(st.R, st.SR, 4).contiguous().float()
+    L.check(lib.pnerf_agg_backward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), _ptr(fwd["decoded"]), _ptr(fwd["weight"]), _ptr(gd),
+                                   _ptr(fwd["saved"]), _ptr(grad_flat), ctypes.byref(pg), _ptr(ws), nws, _stream()), "pnerf_agg_backward")
 
 
 # ------------------------------------------------------------------------------------------ gather (autograd)
@@ -607,13 +669,6 @@ def image_metrics(img, gt, win=11, data_range=2.0, quantize8=True):
 # ------------------------------------------------------------------------------------------ probe pass
 PROBE_RAY_KEYS = (("ray_max_shading_opacity", 1), ("ray_max_sample_loc_w", 3), ("ray_max_far_dist", 1), ("shading_avg_color", 3),
                   ("shading_avg_dir", 3), ("shading_avg_conf", 1), ("shading_avg_embedding", 32))
-
-
-def _dense_arg(t, name, dtype, numel):
-    _need_cuda(t, name)
-    if t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
-        raise ValueError("pointnerf_amd: %s must be a contiguous %s tensor of %d elements, got %s %s" % (name, dtype, numel, t.dtype, list(t.shape)))
-    return t
 
 
 def probe_rays(pts, opacity, weight, sample_loc, sample_pidx, ray_hit, R, SR, K):

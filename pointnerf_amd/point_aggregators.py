@@ -137,11 +137,9 @@ class PointAggregator(nn.Module):
         dev = sampled_embedding.device
         # one Rw2c frame per gathered neighbor ([1,R,SR,K,3,3]: NeuralPoints.forward of a composed scene): render-only
         frames = sampled_Rw2c is not None and sampled_Rw2c.dim() == 6
-        if sampled_Rw2c is not None and sampled_Rw2c.dim() != 2 and not frames:
+        if sampled_Rw2c is not None and sampled_Rw2c.dim() != 2 and tuple(sampled_Rw2c.shape) != (B, R, SR, K, 3, 3):
             raise NotImplementedError("Rw2c must be [3, 3] or the gathered per-point frames [1, R, SR, K, 3, 3], got %s" % list(sampled_Rw2c.shape))
-        if frames and (tuple(sampled_Rw2c.shape) != (B, R, SR, K, 3, 3) or torch.is_grad_enabled()):
-            raise NotImplementedError("per-point Rw2c (scene editing) is render-only: frames [1, R, SR, K, 3, 3] under torch.no_grad() -- the "
-                                      "reference freezes Rw2c and editing never trains")
+        ops.frames_are_render_only(sampled_Rw2c if frames else None, torch.is_grad_enabled())
         # the route's one host read: is there a valid sample at all -- and, with per-point frames, one whose slot 0 is empty?  The kernels take
         # the view direction's frame from slot 0 (point_aggregators.py:495); the query fills slots from 0 on, only a caller-made mask can
         # leave it empty, and the slot-indexed pseudo points would then read ANOTHER sample's frame where the reference reads point 0's

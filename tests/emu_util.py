@@ -22,11 +22,7 @@ def emu_lib():
         spec.loader.exec_module(mod)
         path = mod.build()
         from pointnerf_amd import _lib as L
-        h = ctypes.CDLL(path)
-        for name, (res, args) in L.PROTOTYPES.items():
-            fn = getattr(h, name)
-            fn.restype, fn.argtypes = res, args
-        _handle = h
+        _handle = L.bind(ctypes.CDLL(path), path)
     return _handle
 
 

@@ -105,6 +105,18 @@ def test_missing_library_is_a_hard_error(monkeypatch):
         _lib.lib()
 
 
+def test_library_of_another_abi_version_is_refused(monkeypatch):
+    """same symbol names, other argument lists: a stale libpnerf_hip.so must not be called through this binding's prototypes"""
+    from pointnerf_amd import _lib
+    built = _lib.lib().pnerf_version()
+    assert built == _lib.ABI_VERSION
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI_VERSION", built + 1)
+    with pytest.raises(RuntimeError, match=r"pnerf_version\(\) %d.*stale build" % built):
+        _lib.lib()
+    assert _lib._lib is None
+
+
 def test_ops_refuse_cpu_tensors():
     from pointnerf_amd import ops, config
     from pointnerf_amd.point_aggregators import PointAggregator
@@ -118,19 +130,35 @@ def test_ops_refuse_cpu_tensors():
 
 
 def test_ctypes_structs_mirror_the_header(tmp_path):
-    """The PODs cross the C ABI by pointer: the ctypes mirrors must have the header's sizes and field offsets (plain C, gcc)."""
+    """The PODs cross the C ABI by pointer: EVERY ctypes mirror must have the header's size and the header's offset and size of every field
+    (plain C, gcc).  The C program is generated from the mirrors' own _fields_: a field the header does not have fails to compile."""
     import ctypes
     from pointnerf_amd import _lib
+    typedefs = {_lib.GridParams: "pnerf_grid_params", _lib.Camera: "pnerf_camera", _lib.Points: "pnerf_points", _lib.PointGrads: "pnerf_point_grads",
+                _lib.AdamTensor: "pnerf_adam_tensor", _lib.ViewDesc: "pnerf_view_desc", _lib.MapDesc: "pnerf_map_desc", _lib.Step: "pnerf_step"}
+    mirrors = {c for c in vars(_lib).values() if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+    assert mirrors == set(typedefs), "a Structure of _lib without its header typedef here: %s" % sorted(c.__name__ for c in mirrors ^ set(typedefs))
+    lines, expect = [], []
+    for cls, td in typedefs.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (td, td))
+        expect.append("%s %d" % (td, ctypes.sizeof(cls)))
+        for name, _ in cls._fields_:
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (td, name, td, name, td, name))
+            f = getattr(cls, name)
+            expect.append("%s.%s %d %d" % (td, name, f.offset, f.size))
     src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pnerf.h"\nint main(void) {\n'
-                   'printf("%zu %zu %zu %zu\\n", sizeof(pnerf_grid_params), sizeof(pnerf_camera), sizeof(pnerf_points), sizeof(pnerf_point_grads));\n'
-                   'printf("%zu %zu %zu\\n", offsetof(pnerf_point_grads, ready_event), offsetof(pnerf_points, n), offsetof(pnerf_camera, has_bg));\n'
-                   'return 0; }\n')
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "pnerf.h"\nint main(void) {\n' + "\n".join(lines) + '\nreturn 0; }\n')
     exe = tmp_path / "sizes"
     subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    sizes, offs = [list(map(int, l.split())) for l in subprocess.check_output([str(exe)]).decode().splitlines()]
-    assert sizes == [ctypes.sizeof(_lib.GridParams), ctypes.sizeof(_lib.Camera), ctypes.sizeof(_lib.Points), ctypes.sizeof(_lib.PointGrads)]
-    assert offs == [_lib.PointGrads.ready_event.offset, _lib.Points.n.offset, _lib.Camera.has_bg.offset]
+    assert subprocess.check_output([str(exe)]).decode().splitlines() == expect
+    # ... and the header's structs have no field a mirror lacks: the sizes above agree and every mirror's fields tile its size
+    for cls in typedefs:
+        end = 0
+        for name, _ in cls._fields_:
+            f = getattr(cls, name)
+            assert f.offset - end < 8, (cls.__name__, name)          # (alignment padding only)
+            end = f.offset + f.size
+        assert ctypes.sizeof(cls) - end < 8, cls.__name__
 
 
 def test_querier_reads_query_size_at_call_time(monkeypatch):

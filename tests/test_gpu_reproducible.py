@@ -37,14 +37,13 @@ def test_inference_forward_is_bit_reproducible():
     decoded, weight = torch.empty(R, SR, 4, **f32), torch.empty(R, SR, K, **f32)
     ray_color, opacity, bg_trans, blend_w = torch.empty(R, 3, **f32), torch.empty(R, SR, **f32), torch.empty(R, **f32), torch.empty(R, SR, **f32)
     ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    step = ops.make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
     first, differing = None, []
     for it in range(LAUNCHES):
         ws.fill_(0xFF)                                    # (NaN patterns: nothing may be read that this launch did not write)
-        L.check(lib.pnerf_render_forward(ctypes.byref(cam), ctypes.byref(pts), ops._ptr(packed), ops._ptr(flat), ops._ptr(raydir),
-                                         ops._ptr(dense["sample_loc"]), ops._ptr(dense["sample_pidx"]), ops._ptr(dense["sample_nn"]),
-                                         ops._ptr(dense["valid_list"]), ops._ptr(dense["counters"]), R, SR, K,
+        L.check(lib.pnerf_render_forward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(step),
                                          ops._ptr(decoded), ops._ptr(weight), ops._ptr(ray_color), ops._ptr(opacity), ops._ptr(bg_trans), ops._ptr(blend_w),
-                                         None, n_valid, ops._ptr(ws), nws, ops._stream()), "pnerf_render_forward")
+                                         None, ops._ptr(ws), nws, ops._stream()), "pnerf_render_forward")
         cur = (ws[: n_valid * 256 * 4].clone(), decoded.clone(), ray_color.clone())           # f rows (bytes), decoded, ray colours
         if first is None:
             first = cur
