@@ -1,7 +1,8 @@
 // backward.hip -- backward of the aggregator: colour MLP dgrad, per-neighbor MLP dgrad + gather
 // scatter-add, and the weight-gradient GEMMs.  The four 256-wide layers run on the f16 matrix pipe with two-plane operands
-// (f16x3.h); all gradients inside the aggregator backward carry a per-call power-of-two scale (k_grad_max) so that they sit
-// in the f16 range, and leave it (atomics, weight-gradient reduction) multiplied by its exact inverse.
+// (f16x3.h); inside the aggregator backward every gradient row carries a power-of-two scale so that it sits in the f16 range, and leaves
+// it multiplied by the exact inverse: the rows of the input-gradient chain the scale S_i of their own SAMPLE (pn_sample_scale; atomics into the
+// point gradients x 1 / S_i), the k-major dY planes of the weight-gradient GEMMs -- sums over rows -- the CALL's scale S (k_grad_max; reduction x 1 / S).
 //
 // The reference gets all of this from torch.autograd over ~60 ATen ops (loss.backward() in
 // models/mvs_points_volumetric_model.py:98-118): cuBLAS dgrad/wgrad per nn.Linear, dense
@@ -76,19 +77,78 @@ __device__ __forceinline__ void pn_scale_from_bits(unsigned mb, float &S, float 
     S = __uint_as_float((unsigned)se << 23);
     invS = __uint_as_float((unsigned)(254 - se) << 23);
 }
+// ---- the scale of a SAMPLE's rows.  The chain from d decoded of a sample to every internal dY row of that sample is linear per row, so each row
+// of the two tile kernels is carried at S_i = the rule above applied to the sample's own four gradient components: a ray whose gradient is 10^-6 of
+// the call's largest keeps the 22 bits (and the e4m3 cross terms) that the call's scale gives the largest row only.  S_i >= S (the sample is one of
+// those k_grad_max saw); a sample without a normal, finite gradient takes S.  Where rows of different samples are ADDED (bias sums, d W5, the
+// k-major planes the weight-gradient GEMMs stream) a row is first multiplied by S / S_i, an exact power of two <= 1, so those sums stay at S.
+// Per tile row in LDS (PnRowScale): one 16-byte record [S_i | 1 / S_i | S / S_i | w S_i] (w: the aggregator row's weight, so that the front reads as
+// many words per row as it did with one scale), and behind the records S / S_i as f16 (0 below 2^-24: such a row is below the planes' last bit).
+static_assert(PN_CTILE == PN_TILE, "one row-scale record layout for both tile kernels");
+constexpr int PN_RSC_BYTES = PN_TILE * 16 + PN_TILE * 2;
+__device__ __forceinline__ void pn_sample_scale(const float4 g, float S, float invS, float &Si, float &invSi) {
+    const unsigned mb = __float_as_uint(fmaxf(fmaxf(fabsf(g.x), fabsf(g.y)), fmaxf(fabsf(g.z), fabsf(g.w))));
+    Si = S; invSi = invS;
+    if (mb >= 0x00800000u && mb < 0x7f800000u) {
+        pn_scale_from_bits(mb, Si, invSi);
+        if (Si < S) { Si = S; invSi = invS; }
+    }
+}
+struct PnRowScale {
+    float *p;
+    __device__ __forceinline__ void set(int r, float Si, float invSi, float S, float w = 0.f) const {
+        const float f = S * invSi;
+        *reinterpret_cast<float4 *>(p + 4 * r) = make_float4(Si, invSi, f, w * Si);
+        reinterpret_cast<_Float16 *>(p + 4 * PN_TILE)[r] = (_Float16)f;
+    }
+    __device__ __forceinline__ float S(int r) const { return p[4 * r]; }
+    __device__ __forceinline__ float inv(int r) const { return p[4 * r + 1]; }
+    __device__ __forceinline__ float to_call(int r) const { return p[4 * r + 2]; }
+    __device__ __forceinline__ float wS(int r) const { return p[4 * r + 3]; }
+    __device__ __forceinline__ const char *h8(int rg) const { return reinterpret_cast<const char *>(p + 4 * PN_TILE) + rg * 16; }      // S / S_i of rows 8 rg .. + 7, f16
+};
+// pn_copy_out_kmajor_h (f16x3.h) with every row multiplied by its S / S_i on the way out: the tile holds the rows at their samples' scales, the
+// plane the weight-gradient GEMM streams holds them at the call's.  A power of two: exact, except that a value pushed below 2^-14 is rounded
+// (once more) to the f16 subnormal grid -- the grid the call-wide scale put it on in the first place.
+template <int NF, int XRS = PN_XRS>
+__device__ __forceinline__ void pn_copy_out_kmajor_hs(const char *X, const PnRowScale &rs, uint4 *__restrict__ dst, long long rg0, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int blk = ((lane >> 2) & 3) * XRS + ((lane >> 4) * 16 + (lane & 3) * 4) * 2;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int rg = wave * 2 + i;
+        const char *src = X + rg * 8 * XRS + blk;
+        uint4 *d = dst + (rg0 + rg) * NF;
+        const uint4 fq = *reinterpret_cast<const uint4 *>(rs.h8(rg));
+        const pn_h4 flo = __builtin_bit_cast(pn_h4, make_uint2(fq.x, fq.y)), fhi = __builtin_bit_cast(pn_h4, make_uint2(fq.z, fq.w));
+        uint2 lo[(NF + 63) / 64], hi[(NF + 63) / 64];
+#pragma unroll
+        for (int j = 0; j < (NF + 63) / 64; ++j) { lo[j] = pn_lds_read_tr16(src + j * 128); hi[j] = pn_lds_read_tr16(src + 4 * XRS + j * 128); }
+#pragma unroll
+        for (int j = 0; j < (NF + 63) / 64; ++j) {
+            const int f = lane + 64 * j;
+            if (f < NF) {
+                const uint2 a = __builtin_bit_cast(uint2, __builtin_bit_cast(pn_h4, lo[j]) * flo), b = __builtin_bit_cast(uint2, __builtin_bit_cast(pn_h4, hi[j]) * fhi);
+                pn_f4 t = {__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(b.x), __uint_as_float(b.y)};
+                PN_STREAM_STORE(t, reinterpret_cast<pn_f4 *>(d + f));
+            }
+        }
+    }
+}
 
 // ------------------------------------------------------------------------------ colour backward
 // 64 valid samples per tile, the forward's organisation: d rgb -> d(pre-sigmoid) -> d c3 on the VALU (3 x 128 weights), then the
-// dgrad chain d c3 x Wc3 -> d c2 x Wc2 -> d c1 x Wc1[:, :256] -> d f as two-plane f16 GEMMs on gradients that carry the call's
-// power-of-two scale S (k_grad_max).  The LeakyReLU masks are the forward's sign words (c1, c2) and the saved fp32 c3; d c1..d c3 leave
-// k-major as one f16 plane (scaled) for the weight-gradient GEMMs of these layers, d f as fp32 rows (x 1/S) for k_agg_backward.
-// LDS: the tile, d raw [64][4], and the workgroup's running sums of d Wc4 [3][128], d bc3, d bc2, d bc1 [128] (LDS float adds:
+// dgrad chain d c3 x Wc3 -> d c2 x Wc2 -> d c1 x Wc1[:, :256] -> d f as two-plane f16 GEMMs on gradient rows that carry the power-of-two
+// scale S_i of their own sample (pn_sample_scale).  The LeakyReLU masks are the forward's sign words (c1, c2) and the saved fp32 c3; d c1..d c3 leave
+// k-major as one f16 plane at the CALL's scale S (rows x S / S_i) for the weight-gradient GEMMs of these layers, d f as fp32 rows (x 1 / S_i) for
+// k_agg_backward.
+// LDS: the tile, d raw [64][4] (slot 3: S_i), the rows' scale records, and the workgroup's running sums of d Wc4 [3][128], d bc3, d bc2, d bc1 [128] (LDS float adds:
 // kept in registers they are 45 loop-carried values per thread next to the GEMM's working set)
 // The tile holds 128 columns at most (d c3, d c2, d c1): its rows are 272 bytes apart (68 dwords = 4 mod 64 banks: the GEMM's 16-byte fragment
 // reads of 16 consecutive rows are conflict-free), 35 KB for both planes instead of the 76 KB of the 296-column tile -- THREE workgroups per
 // CU instead of two (the kernel is a chain of short phases with 3.5 us of MFMA work per tile: what it lacks is waves to overlap them).
 constexpr int CB_XRS = 2 * PN_HC + 16, CB_XPL = PN_CTILE * CB_XRS, CB_XBYTES = 2 * CB_XPL;
-constexpr int CB_DRAW = CB_XBYTES, CB_GACC = CB_DRAW + PN_CTILE * 4 * 4, CB_W4 = CB_GACC + 6 * PN_HC * 4, CB_BYTES = CB_W4 + 3 * PN_HC * 4;
+constexpr int CB_DRAW = CB_XBYTES, CB_GACC = CB_DRAW + PN_CTILE * 4 * 4, CB_W4 = CB_GACC + 6 * PN_HC * 4, CB_RSC = CB_W4 + 3 * PN_HC * 4, CB_BYTES = CB_RSC + PN_RSC_BYTES;
 static_assert(3 * CB_BYTES <= 160 * 1024, "three colour workgroups must fit the 160 KB LDS");
 
 // d(pre-activation) = acc * LeakyReLU' (sign bits of the forward's pre-activations, same lane -> element map): two planes
@@ -105,19 +165,20 @@ __device__ __forceinline__ void cb_epilogue(const f32x16 (&acc)[2][2], unsigned 
             pn_x_store4<true, CB_XRS, CB_XPL>(X, row, f0, v[0], v[1], v[2], v[3]);
         }
 }
-// column sums of the tile's first 128 columns (the bias gradient of the layer whose d(pre-activation) the tile holds): thread ->
-// 8 columns x 4 rows
-__device__ __forceinline__ void cb_bias_sums(const char *X, int tid, float *__restrict__ gsum) {
+// column sums of the tile's first 128 columns (the bias gradient of the layer whose d(pre-activation) the tile holds), every row brought to the
+// call's scale first (x S / S_i): thread -> 8 columns x 4 rows
+__device__ __forceinline__ void cb_bias_sums(const char *X, const PnRowScale &rs, int tid, float *__restrict__ gsum) {
     const int c0 = 8 * (tid & 15), r0 = 4 * (tid >> 4);
     float gb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
         const uint4 h = *reinterpret_cast<const uint4 *>(X + (r0 + rr) * CB_XRS + c0 * 2);
         const uint4 m = *reinterpret_cast<const uint4 *>(X + CB_XPL + (r0 + rr) * CB_XRS + c0 * 2);
-        gb[0] = pn_fma2_lo(h.x, m.x, 1.f, gb[0]); gb[1] = pn_fma2_hi(h.x, m.x, 1.f, gb[1]);
-        gb[2] = pn_fma2_lo(h.y, m.y, 1.f, gb[2]); gb[3] = pn_fma2_hi(h.y, m.y, 1.f, gb[3]);
-        gb[4] = pn_fma2_lo(h.z, m.z, 1.f, gb[4]); gb[5] = pn_fma2_hi(h.z, m.z, 1.f, gb[5]);
-        gb[6] = pn_fma2_lo(h.w, m.w, 1.f, gb[6]); gb[7] = pn_fma2_hi(h.w, m.w, 1.f, gb[7]);
+        const float f = rs.to_call(r0 + rr);
+        gb[0] = pn_fma2_lo(h.x, m.x, f, gb[0]); gb[1] = pn_fma2_hi(h.x, m.x, f, gb[1]);
+        gb[2] = pn_fma2_lo(h.y, m.y, f, gb[2]); gb[3] = pn_fma2_hi(h.y, m.y, f, gb[3]);
+        gb[4] = pn_fma2_lo(h.z, m.z, f, gb[4]); gb[5] = pn_fma2_hi(h.z, m.z, f, gb[5]);
+        gb[6] = pn_fma2_lo(h.w, m.w, f, gb[6]); gb[7] = pn_fma2_hi(h.w, m.w, f, gb[7]);
     }
 #pragma unroll
     for (int i = 0; i < 8; ++i) atomicAdd(gsum + c0 + i, gb[i]);
@@ -128,7 +189,8 @@ template <bool WG2>
 __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_cb[];
     char *X = smem_cb;
-    float *draw = reinterpret_cast<float *>(smem_cb + CB_DRAW);          // [64][4] d(pre-sigmoid colour)
+    float *draw = reinterpret_cast<float *>(smem_cb + CB_DRAW);          // [64][4] d(pre-sigmoid colour) | the row's scale S_i
+    const PnRowScale rs{reinterpret_cast<float *>(smem_cb + CB_RSC)};
     const int Ns = a.counters[0] < a.cap_samples ? a.counters[0] : (int)a.cap_samples;
     const float *P = a.params;
     const char *img = reinterpret_cast<const char *>(a.packed);
@@ -140,16 +202,17 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
     float gb4x = 0.f, gb4y = 0.f, gb4z = 0.f;
     // d(pre-sigmoid colour) of this thread's row (threads 0 .. 63) is formed from two dependent gathers (sample id -> decoded / its gradient):
     // requested one tile ahead (the id at the top of the previous tile, the six values behind its first GEMM), so that no tile starts with two
-    // HBM round trips; d bc4 = the column sums of d raw accumulate per row thread and are reduced once at the end
+    // HBM round trips; d bc4 = the column sums of d raw accumulate per row thread and are reduced once at the end.  pgs = d sigma of the sample: only
+    // for the sample's scale, which takes all four components (k_agg_backward derives the same S_i from the same four)
     auto row_sample = [&](long long t) -> long long {
         const long long vs = t * PN_CTILE + threadIdx.x;
         return (threadIdx.x < PN_CTILE && vs < Ns) ? (long long)a.valid_list[vs] : -1;
     };
-    float po[3] = {0.f, 0.f, 0.f}, pg[3] = {0.f, 0.f, 0.f};
+    float po[3] = {0.f, 0.f, 0.f}, pg[3] = {0.f, 0.f, 0.f}, pgs = 0.f;
     auto row_values = [&](long long si) {
         if (si >= 0) {
             const float *o = a.decoded + si * 4, *g = a.grad_decoded + si * 4;
-            po[0] = o[1]; po[1] = o[2]; po[2] = o[3]; pg[0] = g[1]; pg[1] = g[2]; pg[2] = g[3];
+            po[0] = o[1]; po[1] = o[2]; po[2] = o[3]; pgs = g[0]; pg[0] = g[1]; pg[1] = g[2]; pg[2] = g[3];
         }
     };
     long long si_cur = row_sample(blockIdx.x);
@@ -165,13 +228,15 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         const long long grow0 = tile * PN_CTILE;
         PN_LDS_BARRIER();
         if (tid < PN_CTILE) {
-            float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+            float d0 = 0.f, d1 = 0.f, d2 = 0.f, Si = S, invSi = invS;
             if (si_cur >= 0) {
+                pn_sample_scale(make_float4(pgs, pg[0], pg[1], pg[2]), S, invS, Si, invSi);
                 // rgb = sigmoid(raw) * 1.002 - 0.001  ->  d raw = d rgb * 1.002 * s (1 - s)
                 const float s0 = (po[0] + 0.001f) / 1.002f, s1 = (po[1] + 0.001f) / 1.002f, s2 = (po[2] + 0.001f) / 1.002f;
                 d0 = pg[0] * 1.002f * s0 * (1.f - s0); d1 = pg[1] * 1.002f * s1 * (1.f - s1); d2 = pg[2] * 1.002f * s2 * (1.f - s2);
             }
-            *reinterpret_cast<float4 *>(draw + tid * 4) = make_float4(d0, d1, d2, 0.f);
+            *reinterpret_cast<float4 *>(draw + tid * 4) = make_float4(d0, d1, d2, Si);
+            rs.set(tid, Si, invSi, S);
             gb4x += d0; gb4y += d1; gb4z += d2;
         }
         const long long si_next = row_sample(tile + gridDim.x);
@@ -202,7 +267,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
                     gw4[0][i] += d.x * c[i]; gw4[1][i] += d.y * c[i]; gw4[2][i] += d.z * c[i];
                     gb3[i] += u[i];
                 }
-                pn_x_store4<true, CB_XRS, CB_XPL>(X, row, 4 * c4, u[0] * S, u[1] * S, u[2] * S, u[3] * S);
+                pn_x_store4<true, CB_XRS, CB_XPL>(X, row, 4 * c4, u[0] * d.w, u[1] * d.w, u[2] * d.w, u[3] * d.w);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -216,8 +281,8 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         WD3.prefetch(reinterpret_cast<const uint4 *>(img + PKH_DC3), wave, lane);
         PN_LDS_BARRIER();
         // ---- d c2 = (d c3 @ Wc3) * lrelu'(c2)
-        pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X, a.sv.dc3k, tile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X + CB_XPL, a.sv.dc3m, tile * 8, tid);
+        pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X, rs, a.sv.dc3k, tile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X + CB_XPL, rs, a.sv.dc3m, tile * 8, tid);
         const unsigned mw2 = a.sv.cmask[(tile * 2 + 1) * 256 + tid], mw1 = a.sv.cmask[(tile * 2 + 0) * 256 + tid];
         pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 4, 3, CB_XRS, CB_XPL>(X, WD3, lane, acc);
@@ -228,10 +293,10 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         PnGemmW<8, 4, 1, 4, 3> WD2;
         WD2.prefetch(reinterpret_cast<const uint4 *>(img + PKH_DC2), wave, lane);
         PN_LDS_BARRIER();
-        cb_bias_sums(X, tid, gacc + 4 * PN_HC);
+        cb_bias_sums(X, rs, tid, gacc + 4 * PN_HC);
         // ---- d c1 = (d c2 @ Wc2) * lrelu'(c1)
-        pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X, a.sv.dc2k, tile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X + CB_XPL, a.sv.dc2m, tile * 8, tid);
+        pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X, rs, a.sv.dc2k, tile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X + CB_XPL, rs, a.sv.dc2m, tile * 8, tid);
         pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 4, 3, CB_XRS, CB_XPL>(X, WD2, lane, acc);
         PN_LDS_BARRIER();
@@ -239,21 +304,23 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         PnGemmW<8, 8, 2, 1, 3> WD1;
         WD1.prefetch(reinterpret_cast<const uint4 *>(img + PKH_DC1), 2 * wave, lane);
         PN_LDS_BARRIER();
-        cb_bias_sums(X, tid, gacc + 5 * PN_HC);
-        pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X, a.sv.dc1k, tile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_HC, CB_XRS>(X + CB_XPL, a.sv.dc1m, tile * 8, tid);
+        cb_bias_sums(X, rs, tid, gacc + 5 * PN_HC);
+        pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X, rs, a.sv.dc1k, tile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X + CB_XPL, rs, a.sv.dc1m, tile * 8, tid);
         // ---- d f = d c1 @ Wc1[:, :256]
         pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 8, 2, 1, 3, CB_XRS, CB_XPL>(X, WD1, lane, acc);
 #pragma unroll
         for (int fb = 0; fb < 2; ++fb)
 #pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
+            for (int rb = 0; rb < 2; ++rb) {
+                const float ri = rs.inv(32 * rb + (lane & 31));          // (accumulator layout: a lane owns one tile row per row block)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    pn_f4 t = {acc[fb][rb][4 * g] * invS, acc[fb][rb][4 * g + 1] * invS, acc[fb][rb][4 * g + 2] * invS, acc[fb][rb][4 * g + 3] * invS};
+                    pn_f4 t = {acc[fb][rb][4 * g] * ri, acc[fb][rb][4 * g + 1] * ri, acc[fb][rb][4 * g + 2] * ri, acc[fb][rb][4 * g + 3] * ri};
                     PN_REG_STORE(t, reinterpret_cast<pn_f4 *>(a.sv.dfs + (grow0 + 32 * rb + (lane & 31)) * PN_H + pn_d_feat(2 * wave + fb, g, lane)));
                 }
+            }
     }
     PN_LDS_BARRIER();
     {
@@ -274,17 +341,17 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
 
 // ------------------------------------------------------------------------------ aggregator backward
 // One 64-row tile per workgroup at a time, two workgroups per CU (the forward's organisation).  Per tile:
-//   load h4 planes + row metadata + sign words -> alpha head backward (d conf, d alpha pre-activation) -> dY4 in place
+//   load h4 planes + row metadata + sign words + the rows' scales S_i (pn_sample_scale) -> alpha head backward (d conf, d alpha pre-activation) -> dY4 in place
 //   -> four dgrad GEMMs on the f16 pipe, each followed by the LeakyReLU' epilogue that writes the next dY tile; the dY tile of
-//   every layer is copied (transposed to k-major planes) to HBM for the weight-gradient GEMM while its own GEMM runs
+//   every layer is copied (transposed to k-major planes, rows x S / S_i: the call's scale) to HBM for the weight-gradient GEMM while its own GEMM runs
 //   -> layer-3 extras (d colour, d dir) as a ninth feature block, K split over the four waves
 //   -> d X0 (224 columns: the embedding and its encoding) as fp32 in LDS -> PE chain rule -> atomics into the touched points.
 // Bias gradients are not formed here: they are the ones-column of the weight-gradient GEMMs.
-constexpr int BL_ROW = PN_XBYTES, BL_W5 = BL_ROW + 7 * PN_TILE * 4, BL_BYTES = BL_W5 + PN_H * 4;
+constexpr int BL_ROW = PN_XBYTES, BL_RSC = BL_ROW + 10 * PN_TILE * 4, BL_W5 = BL_RSC + PN_RSC_BYTES, BL_BYTES = BL_W5 + PN_H * 4;
 constexpr int LDDX = 228;                      // fp32 row stride of the d X0 tile (over the activation tile's space)
 static_assert(2 * BL_BYTES <= 160 * 1024, "two backward workgroups must fit the 160 KB LDS");
 static_assert(PN_TILE * LDDX * 4 <= PN_XBYTES, "d X0 tile");
-// xyz_grad (XYZG): the d X0 tile holds all 288 columns, and the rows' d(w = wn conf) (scaled) sit behind the alpha head's weights
+// xyz_grad (XYZG): the d X0 tile holds all 288 columns, and the rows' d(w = wn conf) (x S_i) sit behind the alpha head's weights
 constexpr int LDDX_X = 292, BL_GW = BL_BYTES, BL_BYTES_X = BL_GW + PN_TILE * 4;
 static_assert(2 * BL_BYTES_X <= 160 * 1024, "two xyz_grad backward workgroups must fit the 160 KB LDS");
 static_assert(PN_TILE * LDDX_X * 4 <= PN_XBYTES, "d X0 tile (xyz_grad)");
@@ -324,16 +391,17 @@ __device__ __forceinline__ void b_epilogue(const f32x16 (&acc)[PN_NFB][2], const
 // 8 (tid & 31) .. + 7 of rows 8 (tid >> 5) .. + 7, i.e. whole samples): alpha-head backward (d f . h4 per row by the transposing butterfly,
 // d conf, d x), then dY4 = (w d f + d x W5) * LeakyReLU'(h4) written IN PLACE -- a thread only rewrites the elements it alone reads, so
 // there is no barrier between the two halves; d x of a row reaches the 32 lanes that share the row through LDS inside the wave.
-// dfr[2 j], dfr[2 j + 1] = the thread's 8 columns of the d f row of its sample j (KC >= 4), dfb0 = where they come from.  gw5 = d W5 of the thread's 8 columns (scaled).
+// dfr[2 j], dfr[2 j + 1] = the thread's 8 columns of the d f row of its sample j (KC >= 4), dfb0 = where they come from.  gw5 = d W5 of the thread's 8 columns (x S, the
+// call's scale: every row's share x S / S_i).  rs = the rows' scales: dsg, draw and the dY4 rows carry S_i.
 // KC = 0 (round 5): any other K (12 / 6 / 3 of the Barn configuration, ...).  Nothing in the front is per SAMPLE except which d f row a tile row
 // uses, so the same pass serves every K with that index taken at run time (j = row / K - r0 / K; the thread's 8 rows then span up to three
 // samples, whose d f values come straight from memory like KC = 2, 1); the two-pass form it replaces read the tile twice with a barrier between.
 // MIX: dY4 leaves in the mixed format of mixq.h: h (nearest f16) in plane 0 and, in place of the thread's 16 bytes of the h4 residual plane, the
 // group's e4m3 unit [q8(h) x 8 | q8(m 2^11) x 8] -- a thread still rewrites only bytes it alone reads
-// XG (xyz_grad): the row's d w (d sigma alpha + d f . h4, scaled; 0 for a row without a point) also goes to gwf[row] for the weight chain
+// XG (xyz_grad): the row's d w (d sigma alpha + d f . h4, x S_i; 0 for a row without a point) also goes to gwf[row] for the weight chain
 template <int KC, bool MIX = false, bool XG = false>
 __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *w5s, const float *wrow, const float *wnrm, const float *dsg, const float *xrow,
-                                        float *draw, const int *sidx, const int *prow, const float4 (&dfr)[4], const float *dfb0, float S, float invS, int tid,
+                                        float *draw, const int *sidx, const int *prow, const float4 (&dfr)[4], const float *dfb0, const PnRowScale &rs, int tid,
                                         float (&gw5)[8], float &gb5t, unsigned kinv = 0u, float *gwf = nullptr) {
     const int lane = tid & 63, cg = tid & 31, r0 = 8 * (tid >> 5);
     const int j0 = KC == 0 ? pn_row_div(r0, kinv) : 0;
@@ -375,11 +443,11 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
         if ((lane & 3) == 0) {
             float dr = 0.f, gw = 0.f;
             if (sidx[r] >= 0) {
-                const float x = xrow[r], dotf = pd[0] * S;
+                const float x = xrow[r], dotf = pd[0] * rs.S(r);
                 const float alpha = pn_softplus(x), sg = pn_sigmoid(x);
                 const int rp = prow[r];
                 // w = wn * clamp(conf) with a straight-through clamp (gradiant_clamp, point_aggregators.py:722-724)
-                if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * invS + (a.zo_gs ? PnZeroOne(zo_conf, a.zo_eps).grad(a.zo_gs[0]) : 0.f));
+                if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * rs.inv(r) + (a.zo_gs ? PnZeroOne(zo_conf, a.zo_eps).grad(a.zo_gs[0]) : 0.f));
                 if (XG && rp >= 0) gw = dsg[r] * alpha + dotf;
                 dr = dsg[r] * wrow[r] * sg;
             }
@@ -397,8 +465,8 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
         const uint4 h = *reinterpret_cast<const uint4 *>(X + r * PN_XRS + cg * 16);
         const uint4 m = *reinterpret_cast<const uint4 *>(X + PN_XPLANE + r * PN_XRS + cg * 16);
         const bool live = sidx[r] >= 0;          // a row without a sample: its d f values are whatever memory held (0 x NaN is NaN)
-        const float dr = draw[r], w = wrow[r] * S;
-        drsum += dr;
+        const float dr = draw[r], w = rs.wS(r), drc = dr * rs.to_call(r);
+        drsum += drc;
         const float hv[8] = {pn_h_lo(h.x) + pn_h_lo(m.x), pn_h_hi(h.x) + pn_h_hi(m.x), pn_h_lo(h.y) + pn_h_lo(m.y), pn_h_hi(h.y) + pn_h_hi(m.y),
                              pn_h_lo(h.z) + pn_h_lo(m.z), pn_h_hi(h.z) + pn_h_hi(m.z), pn_h_lo(h.w) + pn_h_lo(m.w), pn_h_hi(h.w) + pn_h_hi(m.w)};
         float4 ga, gb;
@@ -408,7 +476,7 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             o[c] = live ? (w * g[c] + dr * w5[c]) * pn_lrelu_grad(hv[c]) : 0.f;
-            gw5[c] += dr * hv[c];
+            gw5[c] += drc * hv[c];
         }
         unsigned oh[4], om[4];
 #pragma unroll
@@ -429,7 +497,7 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
 //   w = wn clamp(conf),  wn = wraw / sum_k wraw_k,  wraw = 1 / max(|dw|, 1e-6)
 // ->  d xyz = Rw2c^T d d[0:3] + camrot d d[3:6] - wraw^2 (d w  w - T wn) dw   (the last term 0 where the clamp holds), T = sum over the
 // sample's rows of d w_k w_k.  The distances are recomputed in fp32 from xyz / sample_loc / camera as the forward forms them (the saved f16
-// plane of X0 has too few bits for a derivative); dxr (the row's d X0) and gwf (d w) carry the call's scale S.  Thread q takes the components
+// plane of X0 has too few bits for a derivative); dxr (the row's d X0) and gwf (d w) carry the scale S_i of the row's sample (invS = its inverse).  Thread q takes the components
 // q and q + 4 (the forward's split) and a quarter of T; three atomics per row.
 __device__ __forceinline__ void b_xyz_row(const BwdXArgs &a, const float *dxr, const float *gwf, const float *wrow, const float *wnrm, const int *sidx,
                                           int rp, int row, int q, int K, unsigned kinv, float invS) {
@@ -494,7 +562,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
     extern __shared__ __attribute__((aligned(16))) char smem_b[];
     char *X = smem_b;
     float *wrow = reinterpret_cast<float *>(smem_b + BL_ROW), *wnrm = wrow + PN_TILE, *draw = wnrm + PN_TILE, *dsg = draw + PN_TILE, *xrow = dsg + PN_TILE;
+    const PnRowScale rs{reinterpret_cast<float *>(smem_b + BL_RSC)};
     int *sidx = reinterpret_cast<int *>(xrow + PN_TILE), *prow = sidx + PN_TILE;
+    float *rdir = reinterpret_cast<float *>(prow + PN_TILE);          // [3][64] the rows' ray directions (for d dir, behind layer 3)
     float *w5s = reinterpret_cast<float *>(smem_b + BL_W5);
     float *dx = reinterpret_cast<float *>(smem_b);
     float *gwf = XYZG ? reinterpret_cast<float *>(smem_b + BL_GW) : nullptr;
@@ -510,7 +580,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
     float S, invS;
     pn_scale_from_bits(a.sv.gscale[0], S, invS);
     if (tid0 < PN_H) w5s[tid0] = P[PO_W5 + tid0];
-    float gw5[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // d W5 of columns 8 (tid & 31) .. + 7 (scaled)
+    float gw5[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // d W5 of columns 8 (tid & 31) .. + 7 (x S)
     float gb5t = 0.f;
     f32x16 acc[PN_NFB][2];
     // row metadata of the tile (threads 0..63: one row each), fetched ONE TILE AHEAD: the d sigma of a row hangs off its sample id, and
@@ -539,12 +609,13 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             const long long o = (long long)(PN_NFB * wave + fb) * 64 + lane;
             m1[fb] = a.sv.lmask[(gtile * 3 + 0) * 512 + o]; m2[fb] = a.sv.lmask[(gtile * 3 + 1) * 512 + o]; m3[fb] = a.sv.lmask[(gtile * 3 + 2) * 512 + o];
         }
-        float dsg_v = 0.f;
+        float4 gd_v = make_float4(0.f, 0.f, 0.f, 0.f);   // d decoded of the row's sample: d sigma, and all four components for the sample's scale
         // the row's ray direction (for d dir, behind layer 3): requested with the burst -- it hangs off the sample id, and as a dependent load
-        // behind the extras' barrier it was 1-2 us of one wave's latency per tile with the other three waves waiting
+        // behind the extras' barrier it was 1-2 us of one wave's latency per tile with the other three waves waiting.  It waits in LDS with the
+        // row's other metadata: three registers less across the layer-4 and layer-3 GEMMs
         float rdx = 0.f, rdy = 0.f, rdz = 0.f;
         if (tid < PN_TILE && rm_cur.x >= 0) {
-            dsg_v = a.grad_decoded[(long long)rm_cur.x * 4];
+            gd_v = *reinterpret_cast<const float4 *>(a.grad_decoded + (long long)rm_cur.x * 4);
             const int r = rm_cur.x / a.SR;
             rdx = a.raydir[3 * r]; rdy = a.raydir[3 * r + 1]; rdz = a.raydir[3 * r + 2];
         }
@@ -565,7 +636,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             sidx[tid] = rm_cur.x; prow[tid] = rm_cur.y;
             wnrm[tid] = __int_as_float(rm_cur.z); wrow[tid] = __int_as_float(rm_cur.w);
             xrow[tid] = ar_cur;
-            dsg[tid] = dsg_v * S;
+            float Si, invSi;
+            pn_sample_scale(gd_v, S, invS, Si, invSi);      // (a row without a sample: zero gradient, the call's scale)
+            rs.set(tid, Si, invSi, S, __int_as_float(rm_cur.w));
+            dsg[tid] = gd_v.x * Si;
+            rdir[tid] = rdx; rdir[PN_TILE + tid] = rdy; rdir[2 * PN_TILE + tid] = rdz;
         }
 #pragma unroll
         for (int i = 0; i < 2 * PN_TILE * 32 / PN_NTHR; ++i) {
@@ -593,11 +668,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         }
         {
             // ---- alpha head backward + dY4 in one pass (b_front): K = 8 / 4 / 2 / 1 with compile-time sample boundaries, any other K at run time
-            if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
-            else if (K == 4) b_front<4, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
-            else if (K == 2) b_front<2, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
-            else if (K == 1) b_front<1, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, 0u, gwf);
-            else b_front<0, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, S, invS, tid, gw5, gb5t, kinv, gwf);
+            if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 4) b_front<4, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 2) b_front<2, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 1) b_front<1, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else b_front<0, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, kinv, gwf);
             PN_TR(pn_trace_bwd, 2);
         }
         // (round 4: the first weight-fragment chunks of every GEMM are requested in FRONT of the barrier that precedes it -- see the forward)
@@ -610,8 +685,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         pn_acc_zero(acc);
         PN_TR(pn_trace_bwd, 4);
         W4.run(X, lane, acc);
-        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy4k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy4m, gtile * 8, tid);
+        pn_copy_out_kmajor_hs<PN_H>(X, rs, a.sv.dy4k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_H>(X + PN_XPLANE, rs, a.sv.dy4m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 5);
         b_epilogue<MIX>(acc, m3, X, wave, lane);
@@ -639,8 +714,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                     make_float4(acce[0][rb][0], acce[0][rb][1], acce[0][rb][2], acce[0][rb][3]);
         }
         W3.run(X, lane, acc);
-        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy3k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy3m, gtile * 8, tid);
+        pn_copy_out_kmajor_hs<PN_H>(X, rs, a.sv.dy3k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_H>(X + PN_XPLANE, rs, a.sv.dy3m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 8);
         b_epilogue<MIX>(acc, m2, X, wave, lane);
@@ -656,15 +731,16 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             }
             float vx, vy, vz, gx = 0.f, gy = 0.f, gz = 0.f;
             if (p >= 0) {
-                rot3(a.cam.rw2c, rdx, rdy, rdz, true, vx, vy, vz);
+                rot3(a.cam.rw2c, rdir[tid], rdir[PN_TILE + tid], rdir[2 * PN_TILE + tid], true, vx, vy, vz);
                 // features (q - v, q . v) with q = dir @ Rw2c^T  ->  d q = dex[3:6] + dex[6] * v ; d dir = d q @ Rw2c
                 rot3(a.cam.rw2c, u.w + v.z * vx, v.x + v.z * vy, v.y + v.z * vz, false, gx, gy, gz);
             }
             // Round 5: the six values go back into the row's (consumed) extras slots and leave three lanes per point: a point's 12 bytes of
             // d colour / d dir are one or two 32-byte sectors instead of three (every lane of the old form hit its own sector)
             float *slot = reinterpret_cast<float *>(X + tid * PN_XRS + 512);
-            *reinterpret_cast<float4 *>(slot) = make_float4(u.x * invS, u.y * invS, u.z * invS, gx * invS);
-            *reinterpret_cast<float2 *>(slot + 4) = make_float2(gy * invS, gz * invS);
+            const float ri = rs.inv(tid);
+            *reinterpret_cast<float4 *>(slot) = make_float4(u.x * ri, u.y * ri, u.z * ri, gx * ri);
+            *reinterpret_cast<float2 *>(slot + 4) = make_float2(gy * ri, gz * ri);
         }
         PN_WAVE_LDS_SYNC();
         if (tid < PN_TILE) {
@@ -689,8 +765,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         pn_acc_zero(acc);
         PN_TR(pn_trace_bwd, 10);
         W2.run(X, lane, acc);
-        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy2k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy2m, gtile * 8, tid);
+        pn_copy_out_kmajor_hs<PN_H>(X, rs, a.sv.dy2k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_H>(X + PN_XPLANE, rs, a.sv.dy2m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 11);
         b_epilogue<MIX>(acc, m1, X, wave, lane);
@@ -725,8 +801,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                 }
             }
         }
-        pn_copy_out_kmajor_h<PN_H>(X, a.sv.dy1k, gtile * 8, tid);
-        if (WG2) pn_copy_out_kmajor_h<PN_H>(X + PN_XPLANE, a.sv.dy1m, gtile * 8, tid);
+        pn_copy_out_kmajor_hs<PN_H>(X, rs, a.sv.dy1k, gtile * 8, tid);
+        if (WG2) pn_copy_out_kmajor_hs<PN_H>(X + PN_XPLANE, rs, a.sv.dy1m, gtile * 8, tid);
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 14);
 #pragma unroll
@@ -765,6 +841,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             float *dr_ = dx + row * LDX;
             const float e[8] = {e0.x, e0.y, e0.z, e0.w, e1.x, e1.y, e1.z, e1.w};
             float go[PN_EPT];
+            const float ri = rs.inv(row);
 #pragma unroll
             for (int i = 0; i < PN_EPT; ++i) {
                 const int dd = PN_EPT * q + i;
@@ -777,7 +854,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
                     g += fr * (t.x * c[f] - t.y * s[f]);
                     fr *= 2.f;
                 }
-                go[i] = g * invS;
+                go[i] = g * ri;
             }
 #pragma unroll
             for (int i = 0; i < PN_EPT; i += 4) *reinterpret_cast<float4 *>(dr_ + PN_EPT * q + i) = make_float4(go[i], go[i + 1], go[i + 2], go[i + 3]);
@@ -789,7 +866,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             const int r = r0w + 2 * j, p = prow[r];
             if (p >= 0) atomicAdd(&a.g_emb[(long long)p * PN_F + col], dx[r * LDX + col]);
         }
-        if constexpr (XYZG) b_xyz_row(a, dx + row * LDX, gwf, wrow, wnrm, sidx, rp, row, q, K, kinv, invS);
+        if constexpr (XYZG) b_xyz_row(a, dx + row * LDX, gwf, wrow, wnrm, sidx, rp, row, q, K, kinv, rs.inv(row));
         PN_TR(pn_trace_bwd, 16);
     }
     // flush the register-resident partial sums: a workgroup that had no tile has nothing to add; the others first add up their eight row

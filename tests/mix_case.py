@@ -20,13 +20,21 @@ def f16(v):
     return np.clip(np.asarray(v, np.float32), -65504, 65504).astype(np.float16).astype(np.float32)
 
 
-def build(K, seed=11, big=False):
+LOW_ROW_STEPS = 17                 # build(low_rows=True): row r is multiplied by 2^-(r % 17), i.e. 2^0 .. 2^-16
+
+
+def build(K, seed=11, big=False, low_rows=False):
+    """low_rows: the 64 rows (bias column included) multiplied by 2^0, 2^-1, ..., 2^-16 cyclically, down into the f16 subnormals: the GEMM's
+    contract is that its input rows arrive PRE-SCALED into the f16 range -- a row that does not loses its residual plane and its e4m3 factors,
+    and device and restatement must lose them alike"""
     rng = np.random.default_rng(seed)
     x = (rng.standard_normal((64, K)) * np.where(rng.random((64, K)) < 0.5, 1.0, 0.01)).astype(np.float32)        # LeakyReLU-like activations
     if big:
         x *= np.float32(40.0)
     w = (rng.uniform(-1, 1, (256, K)) / np.sqrt(K) * 1.7).astype(np.float32)
     x[:, K - 4:] = [1.0, 0.0, 0.0, 0.0]         # a ones column (the bias) and zero padding, like the tiles
+    if low_rows:
+        x *= (2.0 ** -(np.arange(64) % LOW_ROW_STEPS)).astype(np.float32)[:, None]
     return x, w
 
 
@@ -55,3 +63,19 @@ def restate(x, w):
 
 def exact(x, w):
     return x.astype(np.float64) @ w.astype(np.float64).T, np.abs(x.astype(np.float64)) @ np.abs(w.astype(np.float64)).T
+
+
+def check_low_rows(out, x, w, tag):
+    """ROW BY ROW: |out - restatement| <= 5e-6 x that row's max |restatement| (the whole-tile figure of tests/test_gpu_mix.py, per row); prints what
+    each row scale costs against float64, relative to the row's own sum |terms|"""
+    out = np.asarray(out, np.float64)
+    ref = restate(x, w)
+    ex, sab = exact(x, w)
+    d = np.abs(out - ref).max(1) / np.abs(ref).max(1)
+    e = np.abs(out - ex) / sab
+    for j in range(LOW_ROW_STEPS):
+        rows = np.arange(64) % LOW_ROW_STEPS == j
+        print("%s rows x 2^-%-2d  vs restatement %.1e of the row's max   vs float64: rms %.2e max %.2e of the row's sum|terms|" %
+              (tag, j, d[rows].max(), np.sqrt((e[rows] ** 2).mean()), e[rows].max()))
+    assert np.isfinite(out).all()
+    assert d.max() <= 5e-6, (int(d.argmax()), d.max())

@@ -68,6 +68,11 @@ def test_emulated_mixed_tile_gemm_matches_the_numpy_restatement(K):
         e = (out - ex) / sab
         print("K", K, "big", big, "rms err / sum|terms| %.2e  max %.2e" % (np.sqrt((e ** 2).mean()), np.abs(e).max()))
         assert np.abs(e).max() <= 1e-5 and np.sqrt((e ** 2).mean()) <= 2e-6
+    # rows scaled 2^0 .. 2^-16, down into the f16 subnormals: kernel and restatement agree row by row
+    x, w = mix_case.build(K, low_rows=True)
+    out = np.zeros((64, 256), np.float32)
+    assert emu_lib().pnerf_debug_mix_gemm(P(w), K, P(x), P(img), P(out), None) == 0
+    mix_case.check_low_rows(out, x, w, "K %d" % K)
 
 
 def test_emulated_forward_with_e4m3_cross_terms_stays_inside_the_bar():

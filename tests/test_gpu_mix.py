@@ -37,6 +37,23 @@ def test_mixed_tile_gemm_against_restatement_and_float64(K):
         assert np.abs(e).max() <= 1e-5 and np.sqrt((e ** 2).mean()) <= 2e-6
 
 
+@pytest.mark.parametrize("K", [256, 272, 288])
+def test_mixed_tile_gemm_low_rows_match_the_restatement_row_by_row(K):
+    """rows multiplied by 2^0 .. 2^-16 (mix_case.build(low_rows=True)), down into the f16 subnormals: the device agrees with the numpy restatement
+    of the format ROW BY ROW (5e-6 of the row's own largest output) -- what a row that arrives below the f16 range loses, it loses exactly as
+    the format says; the float64 error of every row scale is printed"""
+    dev = torch.device(DEV)
+    lib = L.lib()
+    x, w = mix_case.build(K, low_rows=True)
+    dx, dw = torch.from_numpy(x).to(dev), torch.from_numpy(w).to(dev)
+    img = torch.zeros(lib.pnerf_mlp_packed_bytes(), dtype=torch.uint8, device=dev)
+    out = torch.full((64, 256), float("nan"), device=dev)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+    L.check(lib.pnerf_debug_mix_gemm(P(dw), K, P(dx), P(img), P(out), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "pnerf_debug_mix_gemm")
+    torch.cuda.synchronize()
+    mix_case.check_low_rows(out.cpu().numpy(), x, w, "K %d" % K)
+
+
 def test_mixed_tile_gemm_saturates_instead_of_poisoning():
     """|x| beyond the e4m3 range of a slot (448 for h, ~900 for the residual) and beyond f16 (65504): the cross term degrades, nothing becomes NaN"""
     dev = torch.device(DEV)
