@@ -230,6 +230,47 @@ int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points *pts, const
                          float *d_bg_trans, float *d_blend_w,
                          void *d_saved, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- early ray termination of a RENDER-ONLY pass (the "cut render").  The reference has no counterpart for the cut itself: it shades
+ * every valid sample of every hit ray; what is thresholded here is the transmittance of its ray_march
+ * (models/rendering/diff_ray_marching.py:508-554).  With cutoff c in (0, 1) and a stage width of B = min(stage_samples, SR) slots a ray is
+ * shaded front to back in ceil(SR / B) stages, stage j = slots [jB, min((j+1)B, SR)) (the query packs a ray's samples from slot 0 upwards in
+ * depth order):
+ *   T_r(s) = the exclusive transmittance in front of slot s exactly as pnerf_render_forward's ray march forms it (the same ray-dist
+ *            deltas, u = 1 - op + 1e-10, the product over the slots < s), on the d_decoded values written so far: unshaded samples
+ *            count as sigma = 0;
+ *   ray r is alive at stage 0 (a ray without a valid sample has nothing to shade); alive at stage j >= 1 if alive at j - 1 and T_r(jB) >= c;
+ *   stage j shades the samples with a neighbor of the alive rays in its slots: the launches of pnerf_render_forward on the stage's own
+ *            work list and count (no host read between stages; whatever inference arithmetic is selected; per-point frames as there);
+ *   after the last stage pnerf_render_forward's ray march runs once over the dense d_decoded.
+ * Unshaded samples therefore have d_decoded = d_weight = d_opacity = d_blend_w = 0, and d_bg_trans of a ray that was cut is its
+ * transmittance AT TERMINATION (< c), not the value of the full render.  Error bound: decoded RGB lies in [-0.001, 1.001] (sigmoid * 1.002
+ * - 0.001) and the background in [0, 1]; what is dropped is, up to the 1e-10 terms, a convex combination of such values times T_cut < c, so
+ * every channel of d_ray_color differs from pnerf_render_forward's by less than 1.002 c.  No atomics: two calls give the same bits.
+ *
+ * d_cut_counters [4] i32: [0] = samples shaded, [1] = rays that ended with at least one valid sample unshaded, [2] = [3] = 0.
+ * d_ws as pnerf_render_forward's inference workspace (pnerf_agg_workspace_bytes(step->n_valid_max, K): reused stage after stage);
+ * d_cut_ws holds pnerf_render_cut_workspace_bytes(R, SR).  Inference only (no saved area).  PNERF_E_INVAL: cutoff outside [0, 1),
+ * stage_samples < 1, a null pointer, and everything pnerf_render_forward refuses (the same PNERF_E_UNSUP cases too);
+ * cutoff == 0 runs the body of pnerf_render_forward (d_cut_ws is not used; [0] = step->counters[0]). */
+size_t pnerf_render_cut_workspace_bytes(int R, int SR);
+int pnerf_render_forward_cut(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *step, float cutoff, int stage_samples,
+                             float *d_decoded, float *d_weight, float *d_ray_color, float *d_opacity, float *d_bg_trans, float *d_blend_w,
+                             int32_t *d_cut_counters, void *d_ws, size_t ws_bytes, void *d_cut_ws, size_t cut_ws_bytes, void *stream);
+/* ONE stage of the cut render on caller-supplied dense arrays (d_sample_loc [R,SR,3], d_sample_nn [R,SR], d_ray_hit [R], d_decoded [R,SR,4]
+ * as written by the stages before): the step of stage `stage` (advance T through the slots of stage - 1, decide alive, flag the stage's
+ * slots) and the compaction of the flags.  The transmittance is ray_march's, models/rendering/diff_ray_marching.py:508-554; the cut has no
+ * reference counterpart.  Per-ray state, written by stage 0 and updated by every later one (call the stages in order):
+ *   d_trans [R] f32      T in front of slot stage * B (frozen once the ray has ended)
+ *   d_depth_max [R] f32  running maximum of the perspective depth over the slots < (stage - 1) * B + B (-inf at stage 0)
+ *   d_alive [R] i32      1 = alive; 0 = missed the cloud, or ended with nothing left to shade; 2 = ended with a valid sample unshaded
+ * Outputs: d_flags [R,SR] i32 0/1 (every element written), d_list [max(R*SR,1)] the ascending r * SR + s of the flags, d_counters [8] with
+ * [0] = its length (the words the aggregator launches read).  d_ws holds pnerf_compact_workspace_bytes(R * SR).  cutoff in (0, 1);
+ * PNERF_E_INVAL also for stage * B >= SR. */
+int pnerf_cut_stage(const pnerf_camera *cam, const float *d_sample_loc, const int32_t *d_sample_nn, const int32_t *d_ray_hit,
+                    const float *d_decoded, int R, int SR, float cutoff, int stage_samples, int stage,
+                    float *d_trans, float *d_depth_max, int32_t *d_alive, int32_t *d_flags, int32_t *d_list, int32_t *d_counters,
+                    void *d_ws, size_t ws_bytes, void *stream);
+
 /* Arithmetic of the INFERENCE forward (d_saved == NULL; pnerf_render_forward and pnerf_agg_forward): every fp32 GEMM operand is two f16
  * planes and a multiply-add is 3 MFMA products (default: fp32-class accuracy, sigma / RGB ~1e-6 from an fp32 evaluation) or 2 (the
  * weights' residual plane dropped: a third of the matrix work and half of the weight stream less; measured: rendered ray colour 1e-6 ..

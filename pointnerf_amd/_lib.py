@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1001                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1002                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
@@ -105,6 +105,13 @@ PROTOTYPES = {
     "pnerf_render_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
     # (cam, pts, step, decoded, weight, ray_color, opacity, bg_trans, blend_w, saved, ws, ws_bytes, stream)
     "pnerf_render_forward": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnerf_render_cut_workspace_bytes": (c_size_t, [c_int, c_int]),
+    # (cam, pts, step, cutoff, stage_samples, decoded, weight, ray_color, opacity, bg_trans, blend_w, cut_counters, ws, ws_bytes, cut_ws, cut_ws_bytes, stream)
+    "pnerf_render_forward_cut": (c_int, _STEP_ARGS + [c_f32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    # (cam, sample_loc, sample_nn, ray_hit, decoded, R, SR, cutoff, stage_samples, stage, trans, depth_max, alive, flags, list, counters, ws, ws_bytes, stream)
+    "pnerf_cut_stage": (c_int, [ctypes.POINTER(Camera), c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_f32, c_int, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnerf_set_inference_products": (c_int, [c_int]),
     "pnerf_set_wgrad_planes": (c_int, [c_int]),
     "pnerf_set_cross_terms": (c_int, [c_int]),

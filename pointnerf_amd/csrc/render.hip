@@ -179,6 +179,91 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
     }
 }
 
+// ---- early ray termination of a render-only pass ("cut render", include/pnerf.h: pnerf_render_forward_cut) -------------------------
+// The reference has no counterpart for the cut itself; what is thresholded is ray_march's transmittance (models/rendering/
+// diff_ray_marching.py:508-554) as k_raymarch_forward forms it: the ray-dist deltas of chunk_raydist, u = 1 - op + 1e-10, the product
+// over the slots in front.  A ray is shaded front to back in stages of B slots; the step of stage j advances the ray's transmittance
+// through the slots of stage j - 1 (their sigma is in `decoded` by then; unshaded samples hold 0), drops the ray once T < cutoff, and
+// flags the slots of stage j with a neighbor of the rays still alive.  One wavefront per ray.  Per-ray state between stages: the running
+// T, the running cummax of the perspective depth in front of the next slot to advance through (the ray-dist delta needs it), and
+//   alive: 1 = still shaded, 0 = a miss or ended with nothing left to shade, 2 = ended with at least one valid sample unshaded
+// so a stage reads only its own B slots of sample_loc / decoded (a ray that ends reads the rest of its neighbor counts once).
+struct CutArgs {
+    pnerf_camera cam;
+    const float *sample_loc, *decoded;
+    const int *nn, *hit;
+    int R, SR, B, stage;
+    float cutoff;
+};
+__global__ __launch_bounds__(TPB) void k_cut_stage(CutArgs a, float *__restrict__ T_st, float *__restrict__ cm_st, int *__restrict__ alive_st,
+                                                   int *__restrict__ flags) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (r >= a.R) return;
+    const int SR = a.SR;
+    const long long row = (long long)r * SR;
+    int alive;
+    float T = 1.f, cm_prev = -INFINITY;
+    if (a.stage == 0) alive = (!a.hit || a.hit[r] > 0) ? 1 : 0;      // (no hit flags: a ray without a valid sample flags nothing and keeps T = 1)
+    else {
+        alive = alive_st[r]; T = T_st[r]; cm_prev = cm_st[r];
+        if (alive == 1) {
+            const int s0 = (a.stage - 1) * a.B, s1 = s0 + a.B;             // the previous stage's slots (s1 < SR: this stage exists)
+            const float vs = a.cam.vsize_z;
+            for (int base = s0; base < s1; base += 64) {                   // B need not divide 64: lanes beyond s1 carry neutral elements
+                const int s = base + lane;
+                const bool in = s < s1;
+                float z = -INFINITY, znext = -INFINITY;
+                if (in) z = pers_z(a.cam, a.sample_loc + (row + s) * 3);
+                if (in && s + 1 < SR) znext = pers_z(a.cam, a.sample_loc + (row + s + 1) * 3);
+                const float cm = fmaxf(wave_incl_max(z, lane), cm_prev);   // as chunk_raydist
+                float d = (s + 1 < SR) ? fmaxf(cm, znext) - cm : vs;
+                bool m = d < 1e-8f;
+                if (a.cam.raydist_mode_unit > 0) m = m || (d > 2.f * vs);
+                if (m) d = vs;
+                const bool valid = in && a.nn[row + s] > 0;
+                const float sigma = valid ? a.decoded[(row + s) * 4] : 0.f;
+                const float op = 1.f - expf(-sigma * (valid ? d : 0.f));
+                const float u = in ? (1.f - op + 1e-10f) : 1.f;
+                T *= __shfl(wave_incl_prod(u, lane), 63, 64);
+                cm_prev = __shfl(cm, 63, 64);
+            }
+            if (!(T >= a.cutoff)) {                                        // the ray ends here: does that leave a valid sample unshaded?
+                int left = 0;
+                for (int base = s1; base < SR; base += 64) {
+                    const int s = base + lane;
+                    if (s < SR && a.nn[row + s] > 0) left = 1;
+                }
+                alive = __ballot(left) != 0ull ? 2 : 0;
+            }
+        }
+    }
+    if (lane == 0) { T_st[r] = T; cm_st[r] = cm_prev; alive_st[r] = alive; }
+    const int f0 = a.stage * a.B, f1 = f0 + a.B;
+    for (int base = 0; base < SR; base += 64) {                            // the whole row: the compaction reads every flag
+        const int s = base + lane;
+        if (s < SR) flags[row + s] = (alive == 1 && s >= f0 && s < f1 && a.nn[row + s] > 0) ? 1 : 0;
+    }
+}
+// totals of a cut render, without atomics: out[0] = samples shaded (the stages' list lengths added), out[1] = rays that ended with a
+// valid sample unshaded (alive == 2), out[2] = out[3] = 0.  One workgroup.
+__global__ __launch_bounds__(1024) void k_cut_totals(const int *__restrict__ stage_counters, int n_stages, const int *__restrict__ alive_st, int R,
+                                                     int *__restrict__ out) {
+    __shared__ int red[16];
+    int n = 0;
+    for (int r = threadIdx.x; r < R; r += 1024) n += alive_st[r] == 2 ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int cut = 0, shaded = 0;
+        for (int w = 0; w < 16; ++w) cut += red[w];
+        for (int j = 0; j < n_stages; ++j) shaded += stage_counters[8 * j];
+        out[0] = shaded; out[1] = cut; out[2] = 0; out[3] = 0;
+    }
+}
+
 // ---- row gather / scatter-add (NeuralPoints.forward's index_select and its backward) -----------
 __global__ __launch_bounds__(TPB) void k_gather_rows(const float *__restrict__ src, int n_src, int width, const int *__restrict__ idx,
                                                      long long n_idx, float *__restrict__ dst) {
@@ -474,18 +559,37 @@ static int check_step(const pnerf_camera *cam, const pnerf_points *pts, const pn
     return 0;
 }
 
+// where a forward works, after check_step: the saved area (training) or the inference workspace
+static int agg_scratch(const pnerf_step &st, void *d_saved, void *d_ws, size_t ws_bytes, PnSaved &sv) {
+    if (d_saved) sv = pn_saved_carve(d_saved, st.n_valid_max, st.K);
+    else if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(st.n_valid_max, st.K)) return PNERF_E_WS;
+    else agg_workspace_walk(d_ws, st.n_valid_max, st.K, sv);
+    return 0;
+}
+// decoded / weight are zero wherever no sample is shaded
+static int zero_outputs(const pnerf_step &st, float *d_decoded, float *d_weight, hipStream_t s) {
+    if (hipMemsetAsync(d_decoded, 0, (size_t)st.R * st.SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipMemsetAsync(d_weight, 0, (size_t)st.R * st.SR * st.K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
+    return 0;
+}
 // the aggregator + colour MLP of both forwards, after check_step: works in the saved area (training) or in the inference workspace
 static int agg_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step &st, float *d_decoded, float *d_weight,
                        void *d_saved, void *d_ws, size_t ws_bytes, bool save_x0, hipStream_t s) {
     if (st.R == 0) return 0;
     PnSaved sv;
-    if (d_saved) sv = pn_saved_carve(d_saved, st.n_valid_max, st.K);
-    else if (!d_ws || ws_bytes < pnerf_agg_workspace_bytes(st.n_valid_max, st.K)) return PNERF_E_WS;
-    else agg_workspace_walk(d_ws, st.n_valid_max, st.K, sv);
-    if (hipMemsetAsync(d_decoded, 0, (size_t)st.R * st.SR * 4 * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
-    if (hipMemsetAsync(d_weight, 0, (size_t)st.R * st.SR * st.K * sizeof(float), s) != hipSuccess) return PNERF_E_LAUNCH;
+    int rc = agg_scratch(st, d_saved, d_ws, ws_bytes, sv);
+    if (rc || (rc = zero_outputs(st, d_decoded, d_weight, s)) != 0) return rc;
     if (st.n_valid_max == 0) return 0;
     return pn_agg_forward_launch(cam, pts, st, d_decoded, d_weight, sv, d_saved != nullptr, save_x0, s);
+}
+
+static int raymarch_launch(const pnerf_camera *cam, const pnerf_step *st, const float *d_decoded, float *d_ray_color, float *d_opacity, float *d_bg_trans,
+                           float *d_blend_w, hipStream_t s) {
+    { PnProfScope prof(PNK_RAYMARCH_FWD, s);
+    hipLaunchKernelGGL(k_raymarch_forward, dim3(pn_cdiv(st->R, TPB / 64)), dim3(TPB), 0, s, rm_args(*cam, st->sample_loc, st->sample_nn, d_decoded, st->R, st->SR),
+                       d_ray_color, d_opacity, d_bg_trans, d_blend_w, (float *)nullptr); }
+    PN_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
@@ -496,11 +600,89 @@ extern "C" int pnerf_render_forward(const pnerf_camera *cam, const pnerf_points 
     if (rc || st->R == 0) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = agg_forward(cam, pts, *st, d_decoded, d_weight, d_saved, d_ws, ws_bytes, /*save_x0=*/false, s)) != 0) return rc;
-    { PnProfScope prof(PNK_RAYMARCH_FWD, s);
-    hipLaunchKernelGGL(k_raymarch_forward, dim3(pn_cdiv(st->R, TPB / 64)), dim3(TPB), 0, s, rm_args(*cam, st->sample_loc, st->sample_nn, d_decoded, st->R, st->SR),
-                       d_ray_color, d_opacity, d_bg_trans, d_blend_w, (float *)nullptr); }
+    return raymarch_launch(cam, st, d_decoded, d_ray_color, d_opacity, d_bg_trans, d_blend_w, s);
+}
+
+// ---- the cut render (include/pnerf.h) ---------------------------------------------------------------------------------------------
+namespace {
+// the cut workspace: per-ray state, the stage's flags and work list, 8 counter words per stage (at most SR stages), scan scratch
+struct CutWs { float *T, *cm; int *alive, *flags, *list, *counters, *scan; };
+size_t cut_ws_walk(void *base, int R, int SR, CutWs &w) {
+    const size_t n = (size_t)(R > 0 ? R : 0) * SR;
+    PnCarver cv(base);
+    w.T = cv.take<float>(R); w.cm = cv.take<float>(R); w.alive = cv.take<int>(R);
+    w.flags = cv.take<int>(n); w.list = cv.take<int>(n > 0 ? n : 1); w.counters = cv.take<int>((size_t)8 * SR);
+    w.scan = cv.take<int>(pn_scan_scratch_ints((long long)n));
+    return cv.off;
+}
+// the step of stage `stage` and the compaction of its flags: list = ascending r * SR + s, counters[0] = its length (counters[1..7] = 0)
+int cut_stage_launch(const pnerf_camera &cam, const float *sample_loc, const int *nn, const int *hit, const float *decoded, int R, int SR, float cutoff,
+                     int B, int stage, float *T, float *cm, int *alive, int *flags, int *list, int *counters, int *scan, hipStream_t s) {
+    CutArgs a;
+    a.cam = cam; a.sample_loc = sample_loc; a.decoded = decoded; a.nn = nn; a.hit = hit; a.R = R; a.SR = SR; a.B = B; a.stage = stage; a.cutoff = cutoff;
+    if (hipMemsetAsync(counters, 0, 8 * sizeof(int), s) != hipSuccess) return PNERF_E_LAUNCH;
+    PnProfScope prof(PNK_COMPACT, s);
+    hipLaunchKernelGGL(k_cut_stage, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, a, T, cm, alive, flags);
     PN_CHECK_LAUNCH();
-    return 0;
+    return pn_compact_gt0_i32(flags, (long long)R * SR, list, counters, scan, s);
+}
+}  // namespace
+
+extern "C" size_t pnerf_render_cut_workspace_bytes(int R, int SR) {
+    if (R < 0 || SR <= 0) return 0;
+    CutWs w;
+    return cut_ws_walk(nullptr, R, SR, w);
+}
+
+extern "C" int pnerf_cut_stage(const pnerf_camera *cam, const float *d_sample_loc, const int32_t *d_sample_nn, const int32_t *d_ray_hit,
+                               const float *d_decoded, int R, int SR, float cutoff, int stage_samples, int stage,
+                               float *d_trans, float *d_depth_max, int32_t *d_alive, int32_t *d_flags, int32_t *d_list, int32_t *d_counters,
+                               void *d_ws, size_t ws_bytes, void *stream) {
+    if (!cam || !d_sample_loc || !d_sample_nn || !d_ray_hit || !d_decoded || !d_trans || !d_depth_max || !d_alive || !d_flags || !d_list || !d_counters || !d_ws)
+        return PNERF_E_INVAL;
+    if (R < 0 || SR <= 0 || !(cutoff > 0.f && cutoff < 1.f) || stage_samples < 1 || stage < 0) return PNERF_E_INVAL;
+    const int B = stage_samples < SR ? stage_samples : SR;
+    if ((long long)stage * B >= SR) return PNERF_E_INVAL;
+    if (ws_bytes < pnerf_compact_workspace_bytes((int64_t)R * SR)) return PNERF_E_WS;
+    if (R == 0) return hipMemsetAsync(d_counters, 0, 8 * sizeof(int), (hipStream_t)stream) == hipSuccess ? 0 : PNERF_E_LAUNCH;
+    return cut_stage_launch(*cam, d_sample_loc, d_sample_nn, d_ray_hit, d_decoded, R, SR, cutoff, B, stage, d_trans, d_depth_max, d_alive, d_flags, d_list,
+                            d_counters, (int *)d_ws, (hipStream_t)stream);
+}
+
+extern "C" int pnerf_render_forward_cut(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st, float cutoff, int stage_samples,
+                                        float *d_decoded, float *d_weight, float *d_ray_color, float *d_opacity, float *d_bg_trans, float *d_blend_w,
+                                        int32_t *d_cut_counters, void *d_ws, size_t ws_bytes, void *d_cut_ws, size_t cut_ws_bytes, void *stream) {
+    if (!(cutoff >= 0.f && cutoff < 1.f) || stage_samples < 1) return PNERF_E_INVAL;
+    int rc = check_step(cam, pts, st, ST_RENDER, d_decoded && d_weight && d_ray_color && d_opacity && d_bg_trans && d_blend_w && d_cut_counters);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(d_cut_counters, 0, 4 * sizeof(int), s) != hipSuccess) return PNERF_E_LAUNCH;
+    if (st->R == 0) return 0;
+    if (cutoff == 0.f) {                       // no cut: the body of pnerf_render_forward; every valid sample is shaded
+        if ((rc = agg_forward(cam, pts, *st, d_decoded, d_weight, nullptr, d_ws, ws_bytes, /*save_x0=*/false, s)) != 0) return rc;
+        if (hipMemcpyAsync(d_cut_counters, st->counters, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess) return PNERF_E_LAUNCH;
+        return raymarch_launch(cam, st, d_decoded, d_ray_color, d_opacity, d_bg_trans, d_blend_w, s);
+    }
+    const int R = st->R, SR = st->SR;
+    PnSaved sv;
+    if ((rc = agg_scratch(*st, nullptr, d_ws, ws_bytes, sv)) != 0) return rc;
+    if (!d_cut_ws || cut_ws_bytes < pnerf_render_cut_workspace_bytes(R, SR)) return PNERF_E_WS;
+    CutWs w;
+    cut_ws_walk(d_cut_ws, R, SR, w);
+    if ((rc = zero_outputs(*st, d_decoded, d_weight, s)) != 0) return rc;
+    const int B = stage_samples < SR ? stage_samples : SR, n_stages = pn_cdiv(SR, B);
+    pnerf_step stage_step = *st;               // the same launches as pnerf_render_forward's, on the stage's list and count
+    stage_step.valid_list = w.list;
+    for (int j = 0; j < n_stages; ++j) {
+        stage_step.counters = w.counters + 8 * j;
+        if ((rc = cut_stage_launch(*cam, st->sample_loc, st->sample_nn, /*hit=*/nullptr, d_decoded, R, SR, cutoff, B, j, w.T, w.cm, w.alive, w.flags, w.list,
+                                   w.counters + 8 * j, w.scan, s)) != 0) return rc;
+        if (st->n_valid_max > 0 && (rc = pn_agg_forward_launch(cam, pts, stage_step, d_decoded, d_weight, sv, /*train=*/false, /*save_x0=*/false, s)) != 0) return rc;
+    }
+    { PnProfScope prof(PNK_COMPACT, s);
+    hipLaunchKernelGGL(k_cut_totals, dim3(1), dim3(1024), 0, s, w.counters, n_stages, w.alive, R, d_cut_counters); }
+    PN_CHECK_LAUNCH();
+    return raymarch_launch(cam, st, d_decoded, d_ray_color, d_opacity, d_bg_trans, d_blend_w, s);
 }
 
 extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,

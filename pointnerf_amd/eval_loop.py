@@ -28,12 +28,37 @@ def rays_from_pixels(pixel_idx, intrinsic, camrotc2w):
     return dirs @ camrotc2w[0].T
 
 
+def cut_setting(marcher, transmittance_cutoff=None, cutoff_stage=None):
+    """Context manager: ``marcher.transmittance_cutoff`` / ``marcher.cutoff_stage`` (NeuralPointsRayMarching: early ray termination of
+    render-only passes) set for the duration of a block and restored afterwards; None keeps the current setting."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def scope():
+        prev = (marcher.transmittance_cutoff, marcher.cutoff_stage)
+        if transmittance_cutoff is not None:
+            marcher.transmittance_cutoff = float(transmittance_cutoff)
+        if cutoff_stage is not None:
+            marcher.cutoff_stage = int(cutoff_stage)
+        try:
+            yield marcher
+        finally:
+            marcher.transmittance_cutoff, marcher.cutoff_stage = prev
+    return scope()
+
+
 @torch.no_grad()
-def render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=160000, products=None):
+def render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=160000, products=None, transmittance_cutoff=None,
+                 cutoff_stage=None):
     """Returns (image [h, w, 3] on the device, ray_mask [h*w] bool).  ``products`` = 2 renders with two MFMA products per multiply-add
     (ops.set_inference_products: ~1.5x less matrix work, ray colour within ~2e-5 of the three-product render; the previous setting is
-    restored on return); None keeps the library's current setting."""
+    restored on return); None keeps the library's current setting.  ``transmittance_cutoff`` = c in (0, 1) renders with early ray
+    termination in stages of ``cutoff_stage`` sample slots (``model.transmittance_cutoff`` / ``model.cutoff_stage``, set for this call and
+    restored on return: every channel within 1.002 c of the full render; 0 switches it off); None keeps the model's current setting."""
     from . import ops
+    if transmittance_cutoff is not None or cutoff_stage is not None:
+        with cut_setting(model, transmittance_cutoff, cutoff_stage):
+            return render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=chunk, products=products)
     if products is not None:
         prev = ops.set_inference_products(products)
         try:
@@ -93,7 +118,8 @@ def check_score_names(metrics):
 
 
 @torch.no_grad()
-def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, on_view=None, metrics=()):
+def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, on_view=None, metrics=(), transmittance_cutoff=None,
+               cutoff_stage=None):
     """``test()`` of the training / evaluation scripts (run/train_ft.py:252-414, run/test_ft.py:134-274) around the model
     shell: for every ``test_num_step``-th view render all its rays through ``model.set_input / model.test()``, scatter the
     visuals into H x W canvases by ``pixel_idx``, score the items of ``opt.test_color_loss_items``
@@ -109,8 +135,14 @@ def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, 
     ``metrics`` (default none: the result is what it was without the keyword) names scores of ``image_scores``: each view's
     ``coarse_raycolor`` canvas is scored against its ``gt_image`` canvas on the device, and the means over the views are added to the
     returned dict under "psnr" / "ssim" / "rmse", the keys of the reference's ``report_metrics`` (run/evaluate.py:76).  They are read back
-    once, after the last view."""
+    once, after the last view.
+
+    ``transmittance_cutoff`` / ``cutoff_stage``: early ray termination for these renders (``render_image``), set on
+    ``model.net_ray_marching`` for the duration of the call and restored afterwards; None keeps the current setting."""
     check_score_names(metrics)                       # before any view is rendered
+    if transmittance_cutoff is not None or cutoff_stage is not None:
+        with cut_setting(model.net_ray_marching, transmittance_cutoff, cutoff_stage):
+            return test_views(model, views, opt, height, width, test_num_step=test_num_step, chunk=chunk, on_view=on_view, metrics=metrics)
     model.eval()
     dev = model.device
     items = list(getattr(opt, "test_color_loss_items", ["coarse_raycolor"]))

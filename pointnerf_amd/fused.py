@@ -48,7 +48,7 @@ class FusedRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, env, emb, conf, pdir, color, *mlp_params):
-        # env: dict(cam, xyz, raydir, dense, R, SR, K, n_valid, flat, packed, train, layout[, xyz_grad])
+        # env: dict(cam, xyz, raydir, dense, R, SR, K, n_valid, flat, packed, train, layout[, xyz_grad][, cut])
         ctx.xyz_shape = None
         if env.get("xyz_grad"):
             ctx.xyz_shape = tuple(mlp_params[0].shape)
@@ -61,8 +61,15 @@ class FusedRender(torch.autograd.Function):
         # a step whose saved activations would exceed the arena budget runs its forward without saving anything; the backward then
         # re-runs the forward chunk of rays by chunk of rays (ops.arena_budget_bytes)
         ctx.recompute = bool(env["train"]) and L.lib().pnerf_agg_saved_bytes(env["n_valid"], env["K"]) > ops.arena_budget_bytes()
-        fwd = ops.render_forward(env["cam"], pts, env["packed"], env["flat"], env["raydir"], env["dense"],
-                                 env["R"], env["SR"], env["K"], env["n_valid"], env["train"] and not ctx.recompute)
+        if env.get("cut") is not None:            # (cutoff, stage): the render-only forward with early ray termination (NeuralPointsRayMarching.render_dense)
+            if env["train"]:
+                raise NotImplementedError("transmittance_cutoff is render-only: a training forward shades every sample")
+            fwd = ops.render_forward_cut(env["cam"], pts, env["packed"], env["flat"], env["raydir"], env["dense"],
+                                         env["R"], env["SR"], env["K"], env["n_valid"], *env["cut"])
+            env["cut_counters"] = fwd["cut_counters"]
+        else:
+            fwd = ops.render_forward(env["cam"], pts, env["packed"], env["flat"], env["raydir"], env["dense"],
+                                     env["R"], env["SR"], env["K"], env["n_valid"], env["train"] and not ctx.recompute)
         # only what the backward reads: ray_color must NOT be kept -- the returned tensor's grad_fn is this node, and node -> fwd -> ray_color ->
         # node is a reference cycle that only Python's cycle collector breaks: a training-mode forward that is never back-propagated (an evaluation
         # under enabled gradients) then holds its activation arena (tens of GB) until some later collection

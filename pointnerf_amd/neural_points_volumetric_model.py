@@ -34,6 +34,45 @@ def gradient_clamp(sampled_conf, lo=0.0001, hi=1.0):
 SPECULATE = os.environ.get("PNERF_SPECULATE", "1") != "0"
 
 
+class _CutStats(dict):
+    """``last_stats`` of a cut render: ``n_shaded_samples`` / ``rays_cut`` live in a [4] int32 device tensor that the render wrote behind
+    everything else it enqueued; they are read back on first access (of either), so the render itself gets no additional synchronisation."""
+    _LAZY = ("n_shaded_samples", "rays_cut")
+
+    def __init__(self, plain, cut_counters):
+        super().__init__(plain)
+        self._cut_counters = cut_counters
+        for k in self._LAZY:
+            dict.__setitem__(self, k, None)
+
+    def _resolve(self):
+        if self._cut_counters is not None:
+            host = self._cut_counters.cpu()
+            self._cut_counters = None
+            dict.__setitem__(self, "n_shaded_samples", int(host[0]))
+            dict.__setitem__(self, "rays_cut", int(host[1]))
+
+    def __getitem__(self, key):
+        if key in self._LAZY:
+            self._resolve()
+        return dict.__getitem__(self, key)
+
+    def get(self, key, default=None):
+        return self[key] if key in self else default
+
+    def items(self):
+        self._resolve()
+        return dict.items(self)
+
+    def values(self):
+        self._resolve()
+        return dict.values(self)
+
+    def __repr__(self):
+        self._resolve()
+        return dict.__repr__(self)
+
+
 class NeuralPointsRayMarching(nn.Module):
 
     def __init__(self, tonemap_func=None, render_func=None, blend_func=None, aggregator=None, is_compute_depth=False,
@@ -53,6 +92,13 @@ class NeuralPointsRayMarching(nn.Module):
             if getattr(opt, "which_render_func", "radiance") != "radiance" or getattr(opt, "which_blend_func", "alpha") != "alpha" \
                     or getattr(opt, "which_tonemap_func", "off") != "off":
                 raise NotImplementedError("only radiance / alpha / off (every script's setting) is implemented")
+        # Early ray termination of render-only passes (ours; the reference shades every valid sample of every hit ray): with a cutoff c in
+        # (0, 1) a no-grad render shades each ray front to back in stages of ``cutoff_stage`` sample slots and drops the ray once its
+        # transmittance (ray_march's, models/rendering/diff_ray_marching.py:508-554) is below c -- ops.render_forward_cut; every channel of
+        # the ray colour stays within 1.002 c of the full render, coarse_is_background of a cut ray is its transmittance at termination.
+        # 0 (default): the option is off and every path runs what it ran without it.  ``opt.transmittance_cutoff`` is the initial value.
+        self.transmittance_cutoff = float(getattr(opt, "transmittance_cutoff", 0.0) or 0.0) if opt is not None else 0.0
+        self.cutoff_stage = 16
         self.last_stats = None
         self._pool_rays = 0
         self._pinned_words = None
@@ -63,12 +109,30 @@ class NeuralPointsRayMarching(nn.Module):
             self._pinned_words = torch.empty(n, dtype=torch.int64).pin_memory()
         return self._pinned_words
 
+    def _cut_setting(self, train):
+        """(cutoff, stage) when this render takes the cut route (a render-only pass with transmittance_cutoff > 0), None when the option is
+        off; refuses the passes that need every sample shaded"""
+        if not self.transmittance_cutoff:
+            return None
+        cut = ops.check_cutoff(self.transmittance_cutoff, self.cutoff_stage)
+        if train:
+            raise NotImplementedError("transmittance_cutoff = %g is render-only: a training forward (gradients enabled, or train=True) shades every "
+                                      "sample -- run the render under torch.no_grad() or set transmittance_cutoff back to 0" % cut[0])
+        if getattr(self.opt, "prob", 0) == 1 or bool(getattr(self, "fused_probe", False)):
+            raise NotImplementedError("transmittance_cutoff = %g with the probe outputs (opt.prob == 1 / fused_probe): they need the maximum opacity over "
+                                      "ALL samples of a ray -- set transmittance_cutoff back to 0 for the probe pass" % cut[0])
+        return cut
+
     def render_dense(self, campos, raydir, camrotc2w, near, far, bg_color=None, train=None, zero_one_eps=None):
         """The fused step on all R rays.  Returns (ray_color [R,3], opacity, bg_trans, blend_w, decoded, weight, zo_sum, dense); zo_sum =
         the zero-one regulariser's numerator over the hit rays' conf_coefficient when a training step is given ``zero_one_eps`` (the
-        "render" form of ``_output_forms``; else a constant 0)."""
+        "render" form of ``_output_forms``; else a constant 0).
+        With ``transmittance_cutoff`` > 0 a render-only pass (``train`` false) takes the cut route (``_cut_setting``): samples that were not
+        shaded are 0 in opacity / blend_w / decoded / weight, bg_trans of a cut ray is its transmittance at termination (not the full
+        render's value), and ``last_stats`` carries ``n_shaded_samples`` / ``rays_cut``."""
         opt, npnt, agg = self.opt, self.neural_points, self.aggregator
         train = torch.is_grad_enabled() if train is None else train
+        cut = self._cut_setting(train)
         # xyz_grad > 0: the point positions are a leaf of the fused step (d xyz from k_agg_backward's XYZG instances)
         xyz_leaf = bool(train) and npnt.xyz.requires_grad
         # one Rw2c frame PER POINT (a composed scene, pointnerf_amd.editing): the table goes to the kernels as a device pointer
@@ -105,6 +169,8 @@ class NeuralPointsRayMarching(nn.Module):
             env["xyz_grad"] = True
         if frames is not None:
             env["frames"] = frames
+        if cut is not None:
+            env["cut"] = cut
         leaves = (npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + ((npnt.xyz,) if xyz_leaf else ()) + tuple(mlp_params)
         # The step's one host read (number of valid samples: sizes the activation arena; number of hit rays: shapes of the outputs).
         # Round 4: a TRAINING step whose arena already exists is enqueued BEFORE that read with the arena's capacity as the bound -- every
@@ -133,10 +199,13 @@ class NeuralPointsRayMarching(nn.Module):
         if plan is not None:
             self.sparse_plan = (plan[0], int(got[8]), int(got[9]))
         self.last_stats = dict(n_valid_samples=n_valid, rays_hit=int(got[1]), n_selected=int(got[2]), n_neighbor_rows=int(got[3]), rays=R,
-                               enqueued_before_host_read=out is not None, speculative_result_dropped=dropped)
+                               enqueued_before_host_read=out is not None, speculative_result_dropped=dropped,
+                               n_shaded_samples=n_valid, rays_cut=0)
         if out is None:
             env["n_valid"] = n_valid
             out = FusedRender.apply(env, *leaves)
+        if cut is not None:                                   # the two counts of the cut render: on the device until somebody asks
+            self.last_stats = _CutStats(self.last_stats, env["cut_counters"])
         return out + (dense,)
 
     def _output_forms(self):

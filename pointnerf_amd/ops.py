@@ -424,6 +424,64 @@ def render_forward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, tra
                 blend_w=blend_w, saved=saved)
 
 
+def check_cutoff(cutoff, stage):
+    """(cutoff, stage) of a cut render as numbers, refusing what pnerf_render_forward_cut refuses: a transmittance cutoff outside [0, 1), a
+    stage of less than one sample"""
+    cutoff, stage = float(cutoff), int(stage)
+    if not (0.0 <= cutoff < 1.0):
+        raise ValueError("pointnerf_amd: transmittance_cutoff must lie in [0, 1), got %r" % (cutoff,))
+    if stage < 1:
+        raise ValueError("pointnerf_amd: cutoff_stage must be at least 1, got %r" % (stage,))
+    return cutoff, stage
+
+
+def render_forward_cut(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, cutoff, stage):
+    """pnerf_render_forward_cut: the render-only forward with early ray termination -- rays are shaded front to back in stages of ``stage``
+    sample slots and leave once their transmittance is below ``cutoff`` (include/pnerf.h; the reference has no counterpart, the transmittance
+    is ray_march's, models/rendering/diff_ray_marching.py:508-554).  Returns render_forward's dict (saved = None; samples that were not
+    shaded are 0 in decoded / weight / opacity / blend_w, bg_trans of a cut ray is its transmittance at termination) plus ``cut_counters``,
+    a [4] int32 device tensor: samples shaded, rays that ended with a valid sample unshaded, 0, 0.  No host read."""
+    cutoff, stage = check_cutoff(cutoff, stage)
+    lib = L.lib()
+    dev = raydir.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    decoded = torch.empty(R, SR, 4, **f32); weight = torch.empty(R, SR, K, **f32)
+    ray_color = torch.empty(R, 3, **f32); opacity = torch.empty(R, SR, **f32)
+    bg_trans = torch.empty(R, **f32); blend_w = torch.empty(R, SR, **f32)
+    cut_counters = torch.empty(4, dtype=torch.int32, device=dev)
+    st = make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
+    _, ws, nws = _forward_scratch(n_valid, K, False, dev)
+    ncut = lib.pnerf_render_cut_workspace_bytes(R, SR) if cutoff > 0 else 0
+    cut_ws = torch.empty(ncut, dtype=torch.uint8, device=dev) if ncut else None
+    L.check(lib.pnerf_render_forward_cut(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), cutoff, stage,
+                                         _ptr(decoded), _ptr(weight), _ptr(ray_color), _ptr(opacity), _ptr(bg_trans), _ptr(blend_w),
+                                         _ptr(cut_counters), _ptr(ws), nws, _ptr(cut_ws), ncut, _stream()), "pnerf_render_forward_cut")
+    return dict(decoded=decoded, weight=weight, ray_color=ray_color, opacity=opacity, bg_trans=bg_trans, blend_w=blend_w, saved=None,
+                cut_counters=cut_counters)
+
+
+def cut_stage(cam, sample_loc, sample_nn, ray_hit, decoded, cutoff, stage_samples, stage, state=None):
+    """pnerf_cut_stage: one stage of the cut render on dense arrays (sample_loc [R,SR,3], sample_nn [R,SR] i32, ray_hit [R] i32, decoded
+    [R,SR,4] as the earlier stages left it).  ``state`` = the dict a previous stage returned (None for stage 0); returns
+    dict(trans [R], depth_max [R], alive [R] i32 -- the per-ray state, updated in place --, flags [R,SR] i32, list, counters [8] i32)."""
+    R, SR = int(sample_nn.shape[0]), int(sample_nn.shape[1])
+    f32, i32 = torch.float32, torch.int32
+    _dense_arg(sample_loc, "sample_loc", f32, R * SR * 3); _dense_arg(sample_nn, "sample_nn", i32, R * SR)
+    _dense_arg(ray_hit, "ray_hit", i32, R); _dense_arg(decoded, "decoded", f32, R * SR * 4)
+    dev = sample_nn.device
+    if state is None:
+        state = dict(trans=torch.empty(R, dtype=f32, device=dev), depth_max=torch.empty(R, dtype=f32, device=dev), alive=torch.empty(R, dtype=i32, device=dev))
+    out = dict(trans=state["trans"], depth_max=state["depth_max"], alive=state["alive"], flags=torch.empty(R, SR, dtype=i32, device=dev),
+               list=torch.empty(max(R * SR, 1), dtype=i32, device=dev), counters=torch.empty(8, dtype=i32, device=dev))
+    lib = L.lib()
+    nws = lib.pnerf_compact_workspace_bytes(R * SR)
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    L.check(lib.pnerf_cut_stage(ctypes.byref(cam), _ptr(sample_loc), _ptr(sample_nn), _ptr(ray_hit), _ptr(decoded), R, SR, float(cutoff), int(stage_samples),
+                                int(stage), _ptr(out["trans"]), _ptr(out["depth_max"]), _ptr(out["alive"]), _ptr(out["flags"]), _ptr(out["list"]),
+                                _ptr(out["counters"]), _ptr(ws), nws, _stream()), "pnerf_cut_stage")
+    return out
+
+
 def render_backward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, fwd, grad_ray_color, grad_flat, grads, ready_event=None, zero_one=None):
     """pnerf_render_backward: accumulates into grad_flat (MLP) and grads = dict(points_embeding=..., points_conf=...,
     points_dir=..., points_color=...) (device tensors, same shapes as the parameters); an ``xyz`` entry ([N,3] or [1,N,3]) receives d xyz
