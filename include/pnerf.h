@@ -448,6 +448,35 @@ int pnerf_probe_hole_mask(const int8_t *d_ray_mask, const float *d_max_opacity, 
                           const float *d_gt, const uint8_t *d_edge, const float *bg3_host, int H, int W, float opacity_thresh,
                           float far_thresh, int32_t *d_flags, void *stream);
 
+/* ---- per-ray depth and opacity maps of a render-only pass, on the renderer's dense results.
+ *
+ * pnerf_ray_geometry: the depth the reference's `is_compute_depth` was meant to return (models/neural_points_volumetric_model.py:318-322:
+ * sum_s blend_weight ray_ts / (sum_s blend_weight + 1e-6); `ray_ts` is undefined there), with the camera-z depth of a sample in the place
+ * of ray_ts, plus the accumulated opacity and the median depth, from the DENSE tensors of pnerf_query / pnerf_render_forward (d_sample_loc
+ * [R,SR,3], d_sample_nn [R,SR], d_ray_hit [R], d_opacity [R,SR], d_blend_w [R,SR]; opacity, blend weight and transmittance are ray_march's,
+ * models/rendering/diff_ray_marching.py:508-554, read back and not recomputed).  For a ray with d_ray_hit[r] > 0, over the slots s < SR:
+ *   z_s = ((d_sample_loc[r,s] - cam->campos) @ cam->camrot)[2],  valid_s = d_sample_nn[r,s] > 0,
+ *   T_s = prod_{j <= s} (1 - d_opacity[r,j] + 1e-10f)  (a wave-inclusive product per 64 slots times the product carried in front, as the ray march);
+ *   d_acc [R] = sum_s d_blend_w[r,s]      d_depth_sum [R] = sum over the valid s of d_blend_w[r,s] z_s (an empty slot's position is not read)
+ *   d_depth [R] = d_depth_sum / (d_acc + 1e-6f)
+ *   d_median_slot [R] i32 = the lowest valid s with T_s < 0.5, or -1;   d_median_depth [R] = z there, or 0
+ * A ray with d_ray_hit[r] <= 0 gets zeros and -1; its rows are not read.  The sums are per-lane partial sums over the 64-slot chunks met in
+ * one xor butterfly; no atomics: two calls give the same bits.  Of `cam` only campos and camrot are read.
+ * PNERF_E_INVAL: R < 0, SR < 1, a null pointer (cam always; the arrays while R > 0).  R == 0: nothing is enqueued. */
+int pnerf_ray_geometry(const pnerf_camera *cam, const float *d_sample_loc, const int32_t *d_sample_nn, const int32_t *d_ray_hit,
+                       const float *d_opacity, const float *d_blend_w, int R, int SR, float *d_acc, float *d_depth_sum, float *d_depth,
+                       float *d_median_depth, int32_t *d_median_slot, void *stream);
+/* pnerf_geometry_canvas: the per-pixel fill of the three maps for one chunk of n_rays rays (no reference counterpart; the reference's test
+ * loop scatters its visuals by pixel_idx, run/train_ft.py:316-320): ray i goes to pixel (px, py) = d_pixel_idx[i] ([n_rays,2] i32) of the
+ * three [H,W] canvases, canvas[py * W + px] = d_depth / d_median_depth / d_acc [i], or 0 where d_ray_mask[i] <= 0 ([n_rays] i8; NULL: every
+ * ray counts as a hit).  No other pixel is touched.  A pixel outside the image writes nothing and stores PNERF_E_INVAL in *d_flag (i32 on
+ * the device; zero it once, before the first chunk of an image, and read it with the canvases: the call itself never reads it, so the
+ * chunks of an image are enqueued without a host read in between).  PNERF_E_INVAL from the call: n_rays < 0, H or W <= 0, a null pointer
+ * other than d_ray_mask while n_rays > 0. */
+int pnerf_geometry_canvas(const int32_t *d_pixel_idx, const int8_t *d_ray_mask, const float *d_depth, const float *d_median_depth,
+                          const float *d_acc, int n_rays, int H, int W, float *d_depth_canvas, float *d_median_canvas, float *d_acc_canvas,
+                          int32_t *d_flag, void *stream);
+
 /* ---- diagnostics: ONE v_mfma_f32_32x32x16_f16, D = A B with caller-built fragments: d_a / d_b [64 lanes][8] f16 (lane l holds
  * A[l & 31][8 (l >> 5) .. + 7] resp. B[8 (l >> 5) .. + 7][l & 31]), d_out [64 lanes][16] f32 (register r of lane l =
  * D[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31]).  The tests pin with it the fragment layout and the un-flushed handling of f16

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1002                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1003                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
@@ -134,6 +134,12 @@ PROTOTYPES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_probe_hole_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_f32), c_int, c_int,
                                       c_f32, c_f32, c_void_p, c_void_p]),
+    # (cam, sample_loc, sample_nn, ray_hit, opacity, blend_w, R, SR, acc, depth_sum, depth, median_depth, median_slot, stream)
+    "pnerf_ray_geometry": (c_int, [ctypes.POINTER(Camera), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (pixel_idx, ray_mask, depth, median_depth, acc, n_rays, H, W, depth_canvas, median_canvas, acc_canvas, flag, stream)
+    "pnerf_geometry_canvas": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mfma_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mix_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mfma_rate": (c_int, [c_int, c_int, c_void_p, ctypes.POINTER(ctypes.c_double), c_void_p]),

@@ -47,28 +47,80 @@ def cut_setting(marcher, transmittance_cutoff=None, cutoff_stage=None):
     return scope()
 
 
+def geometry_setting(marcher, on=True):
+    """Context manager: ``marcher.ray_geometry`` (NeuralPointsRayMarching: depth and opacity maps of render-only passes) set for the duration of a
+    block and restored afterwards."""
+    import contextlib
+
+    @contextlib.contextmanager
+    def scope():
+        prev = marcher.ray_geometry
+        marcher.ray_geometry = bool(on)
+        try:
+            yield marcher
+        finally:
+            marcher.ray_geometry = prev
+    return scope()
+
+
+GEOMETRY_MAPS = (("depth", "coarse_depth"), ("median_depth", "coarse_median_depth"), ("acc", "coarse_acc"))
+
+
+class _GeometryCanvases:
+    """the three [h, w] maps of one view, filled chunk by chunk through ops.geometry_canvas (one launch per chunk, nothing read in between);
+    ``maps()`` reads the library's out-of-range flag -- the one host read -- and hands the canvases out"""
+
+    def __init__(self, h, w, device):
+        from . import ops
+        self.ops = ops
+        words = torch.zeros(3 * h * w + 1, dtype=torch.float32, device=device)          # the canvases and the flag word: one fill
+        self.canvas = words[:3 * h * w].view(3, h, w)
+        self.flag = words[3 * h * w:].view(torch.int32)
+
+    def fill(self, pixel_idx_i32, ray_mask, full):
+        """``full`` = a fill_invalid'ed output with the three keys [1, n, 1]; pixel_idx_i32 [n, 2]; ray_mask [n] int8"""
+        d, m, a = (full[key][0, :, 0] for _, key in GEOMETRY_MAPS)
+        self.ops.geometry_canvas(pixel_idx_i32, ray_mask, d, m, a, (self.canvas[0], self.canvas[1], self.canvas[2]), flag=self.flag)
+
+    def maps(self):
+        self.ops.check_canvas_flag(self.flag)
+        return {name: self.canvas[i] for i, (name, _) in enumerate(GEOMETRY_MAPS)}
+
+
 @torch.no_grad()
 def render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=160000, products=None, transmittance_cutoff=None,
-                 cutoff_stage=None):
+                 cutoff_stage=None, geometry=False):
     """Returns (image [h, w, 3] on the device, ray_mask [h*w] bool).  ``products`` = 2 renders with two MFMA products per multiply-add
     (ops.set_inference_products: ~1.5x less matrix work, ray colour within ~2e-5 of the three-product render; the previous setting is
     restored on return); None keeps the library's current setting.  ``transmittance_cutoff`` = c in (0, 1) renders with early ray
     termination in stages of ``cutoff_stage`` sample slots (``model.transmittance_cutoff`` / ``model.cutoff_stage``, set for this call and
-    restored on return: every channel within 1.002 c of the full render; 0 switches it off); None keeps the model's current setting."""
+    restored on return: every channel within 1.002 c of the full render; 0 switches it off); None keeps the model's current setting.
+    ``geometry`` = True returns (image, ray_mask, maps) with maps = dict(depth, median_depth, acc), [h, w] float32 each: the per-ray depth and
+    opacity maps of ``model.ray_geometry`` (set for this call and restored on return), written into the canvases by ops.geometry_canvas, 0 where
+    the ray missed.  False (default) launches nothing new and returns the pair."""
     from . import ops
     if transmittance_cutoff is not None or cutoff_stage is not None:
         with cut_setting(model, transmittance_cutoff, cutoff_stage):
-            return render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=chunk, products=products)
+            return render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=chunk, products=products, geometry=geometry)
     if products is not None:
         prev = ops.set_inference_products(products)
         try:
-            return render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=chunk)
+            return render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk=chunk, geometry=geometry)
         finally:
             ops.set_inference_products(prev)
+    if geometry:
+        with geometry_setting(model, True):
+            return _render_chunks(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk, True)
+    return _render_chunks(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk, False)
+
+
+def _render_chunks(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color, chunk, geometry):
     dev = campos.device
     pix = pixel_grid(h, w, dev)
     canvas = torch.empty(h * w, 3, device=dev)
     hit = torch.empty(h * w, dtype=torch.bool, device=dev)
+    if geometry:
+        geo, pix_i = _GeometryCanvases(h, w, dev), pix[0].to(torch.int32)
     for k in range(0, h * w, chunk):
         pi = pix[:, k:k + chunk]
         raydir = rays_from_pixels(pi, intrinsic.to(dev), camrotc2w)
@@ -77,7 +129,23 @@ def render_image(model, campos, camrotc2w, intrinsic, h, w, near, far, bg_color,
         full = fill_invalid(out, bg_color)
         canvas[k:k + chunk] = full["coarse_raycolor"][0]
         hit[k:k + chunk] = out["ray_mask"][0] > 0
+        if geometry:
+            geo.fill(pix_i[k:k + chunk], out["ray_mask"][0], full)
+    if geometry:
+        return canvas.view(h, w, 3), hit, geo.maps()
     return canvas.view(h, w, 3), hit
+
+
+def depth_points(depth_map, campos, camrotc2w, intrinsic):
+    """World positions [n, 3] of the pixels of a [h, w] depth map with depth > 0, in row-major pixel order: campos + depth * raydir with
+    ``rays_from_pixels``' un-normalised directions (their camera-z component is 1, so the camera-z depth of render_image's maps IS the ray
+    parameter).  Plain tensor plumbing on the map's device; the boolean selection is its one host synchronisation."""
+    h, w = int(depth_map.shape[0]), int(depth_map.shape[1])
+    dev = depth_map.device
+    dirs = rays_from_pixels(pixel_grid(h, w, dev), intrinsic.to(dev), camrotc2w.to(dev))[0]          # [h*w, 3]
+    d = depth_map.reshape(-1)
+    keep = d > 0
+    return campos.to(dev).reshape(1, 3) + d[keep][:, None] * dirs[keep]
 
 
 def psnr(img, gt):
@@ -119,7 +187,7 @@ def check_score_names(metrics):
 
 @torch.no_grad()
 def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, on_view=None, metrics=(), transmittance_cutoff=None,
-               cutoff_stage=None):
+               cutoff_stage=None, geometry=False):
     """``test()`` of the training / evaluation scripts (run/train_ft.py:252-414, run/test_ft.py:134-274) around the model
     shell: for every ``test_num_step``-th view render all its rays through ``model.set_input / model.test()``, scatter the
     visuals into H x W canvases by ``pixel_idx``, score the items of ``opt.test_color_loss_items``
@@ -138,11 +206,20 @@ def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, 
     once, after the last view.
 
     ``transmittance_cutoff`` / ``cutoff_stage``: early ray termination for these renders (``render_image``), set on
-    ``model.net_ray_marching`` for the duration of the call and restored afterwards; None keeps the current setting."""
+    ``model.net_ray_marching`` for the duration of the call and restored afterwards; None keeps the current setting.
+
+    ``geometry`` = True adds ``coarse_depth`` / ``coarse_median_depth`` / ``coarse_acc`` canvases, [height, width] float32, to the visuals handed
+    to ``on_view`` (``model.net_ray_marching.ray_geometry``, set for the duration of the call; ops.geometry_canvas fills them); the returned
+    scores are what they are without it."""
     check_score_names(metrics)                       # before any view is rendered
     if transmittance_cutoff is not None or cutoff_stage is not None:
         with cut_setting(model.net_ray_marching, transmittance_cutoff, cutoff_stage):
-            return test_views(model, views, opt, height, width, test_num_step=test_num_step, chunk=chunk, on_view=on_view, metrics=metrics)
+            return test_views(model, views, opt, height, width, test_num_step=test_num_step, chunk=chunk, on_view=on_view, metrics=metrics,
+                              geometry=geometry)
+    if geometry and not model.net_ray_marching.ray_geometry:
+        with geometry_setting(model.net_ray_marching, True):
+            return test_views(model, views, opt, height, width, test_num_step=test_num_step, chunk=chunk, on_view=on_view, metrics=metrics,
+                              geometry=True)
     model.eval()
     dev = model.device
     items = list(getattr(opt, "test_color_loss_items", ["coarse_raycolor"]))
@@ -157,6 +234,8 @@ def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, 
         edge = torch.zeros([height, width], dtype=torch.bool, device=dev)
         edge[pl[:, 1], pl[:, 0]] = True
         visuals, ray_masks = {}, []
+        if geometry:
+            geo, pix_i = _GeometryCanvases(height, width, dev), pl.to(torch.int32)
         for k in range(0, total, chunk):
             data = {kk: vv for kk, vv in view.items() if kk != "gt_mask"}
             data["raydir"] = raydir[:, k:k + chunk, :]
@@ -172,7 +251,12 @@ def test_views(model, views, opt, height, width, test_num_step=1, chunk=160000, 
                     visuals[key] = torch.zeros((height, width, 3), dtype=value.dtype, device=dev)
                 visuals[key][pid[:, 1], pid[:, 0], :] = value[0]
             ray_masks.append(model.output["ray_mask"] > 0)
+            if geometry:
+                geo.fill(pix_i[k:k + chunk], model.output["ray_mask"][0], model.output)
         ray_masks = torch.cat(ray_masks, dim=1)                                   # [1, P]
+        if geometry:
+            maps = geo.maps()
+            visuals.update({key: maps[name] for name, key in GEOMETRY_MAPS})
         gt_rays = view["gt_image"].to(dev).reshape(-1, 3)
         gt_canvas = torch.zeros((height * width, 3), dtype=torch.float32, device=dev)
         gt_canvas[edge.reshape(-1)] = gt_rays            # rays must come in row-major pixel order (the datasets' no_crop grid), :332-333

@@ -762,6 +762,81 @@ def probe_hole_flags(ray_mask, max_opacity, far_dist, raycolor, gt, edge, bg, op
     return flags
 
 
+# ------------------------------------------------------------------------------------------ depth and opacity maps
+RAY_GEOMETRY_KEYS = ("acc", "depth_sum", "depth", "median_depth", "median_slot")
+
+
+def ray_geometry(cam, sample_loc, sample_nn, ray_hit, opacity, blend_w):
+    """pnerf_ray_geometry: per-ray accumulated opacity, expected camera-z depth and median depth of a render-only pass from the renderer's
+    dense tensors (sample_loc [R,SR,3], sample_nn [R,SR] i32, ray_hit [R] i32, opacity / blend_w [R,SR] as render_forward returned them;
+    ``cam`` = make_camera(...) of the view), one launch, no host read.  The depth is the one the reference's ``is_compute_depth`` was meant to
+    give (neural_points_volumetric_model.py:318-322, with the camera-z depth for its undefined ``ray_ts``) on ray_march's blend weights
+    (diff_ray_marching.py:508-554).  Returns dict(acc, depth_sum, depth = depth_sum / (acc + 1e-6), median_depth: [R] f32; median_slot: [R]
+    i32, the lowest valid slot behind which the transmittance is below 0.5, -1 and depth 0 without one); rays that missed get zeros and -1.
+    The four float tensors are the rows of ONE [4, R] allocation, handed out as well under "_rows" (in the order of RAY_GEOMETRY_KEYS), so that a
+    caller that compacts them does it with one gather."""
+    _need_cuda(sample_nn, "sample_nn")
+    if sample_nn.dim() != 2:
+        raise ValueError("pointnerf_amd: sample_nn must be [R, SR], got %s" % (list(sample_nn.shape),))
+    R, SR = int(sample_nn.shape[0]), int(sample_nn.shape[1])
+    f32, i32 = torch.float32, torch.int32
+    _dense_arg(sample_loc, "sample_loc", f32, R * SR * 3); _dense_arg(sample_nn, "sample_nn", i32, R * SR); _dense_arg(ray_hit, "ray_hit", i32, R)
+    _dense_arg(opacity, "opacity", f32, R * SR); _dense_arg(blend_w, "blend_w", f32, R * SR)
+    dev = sample_nn.device
+    for name, t in (("sample_loc", sample_loc), ("ray_hit", ray_hit), ("opacity", opacity), ("blend_w", blend_w)):
+        if t.device != dev:
+            raise ValueError("pointnerf_amd: %s is on %s, sample_nn on %s" % (name, t.device, dev))
+    rows = torch.empty(4, R, dtype=f32, device=dev)
+    out = {k: rows[i] for i, k in enumerate(RAY_GEOMETRY_KEYS[:4])}
+    out["median_slot"] = torch.empty(R, dtype=i32, device=dev)
+    L.check(L.lib().pnerf_ray_geometry(ctypes.byref(cam), _ptr(sample_loc), _ptr(sample_nn), _ptr(ray_hit), _ptr(opacity), _ptr(blend_w), R, SR,
+                                       *[_ptr(out[k]) for k in RAY_GEOMETRY_KEYS], _stream()), "pnerf_ray_geometry")
+    out["_rows"] = rows
+    return out
+
+
+def geometry_canvas(pixel_idx, ray_mask, depth, median_depth, acc, canvases, flag=None):
+    """pnerf_geometry_canvas: the values of one chunk of rays written into the three [H, W] float32 canvases ``canvases`` = (depth, median_depth,
+    acc) at the rays' pixels: pixel_idx [n, 2] (px, py; converted to int32 when it is not), ray_mask [n] int8 or None (a ray with mask <= 0
+    writes 0), depth / median_depth / acc [n] f32.  One launch in the place of three index-puts; no other pixel is touched.
+    A pixel outside the image is an error the DEVICE finds: with ``flag`` = None the call reads its flag back and raises; a caller that fills an
+    image in several chunks passes ``flag`` = canvas_flag(device) to every call (nothing is read in between) and calls check_canvas_flag(flag)
+    once, when it reads the canvases."""
+    _need_cuda(pixel_idx, "pixel_idx")
+    n = int(pixel_idx.numel()) // 2
+    if pixel_idx.dtype != torch.int32 or not pixel_idx.is_contiguous():
+        pixel_idx = pixel_idx.to(torch.int32).contiguous()
+    _dense_arg(pixel_idx, "pixel_idx", torch.int32, n * 2)
+    if ray_mask is not None:
+        _dense_arg(ray_mask, "ray_mask", torch.int8, n)
+    f32 = torch.float32
+    _dense_arg(depth, "depth", f32, n); _dense_arg(median_depth, "median_depth", f32, n); _dense_arg(acc, "acc", f32, n)
+    if len(canvases) != 3 or canvases[0].dim() != 2:
+        raise ValueError("pointnerf_amd: canvases must be three [H, W] tensors (depth, median_depth, acc)")
+    H, W = int(canvases[0].shape[0]), int(canvases[0].shape[1])
+    for name, t in zip(("depth canvas", "median_depth canvas", "acc canvas"), canvases):
+        _dense_arg(t, name, f32, H * W)
+    own = flag is None
+    if own:
+        flag = canvas_flag(pixel_idx.device)
+    _dense_arg(flag, "flag", torch.int32, 1)
+    L.check(L.lib().pnerf_geometry_canvas(_ptr(pixel_idx), _ptr(ray_mask), _ptr(depth), _ptr(median_depth), _ptr(acc), n, H, W,
+                                          _ptr(canvases[0]), _ptr(canvases[1]), _ptr(canvases[2]), _ptr(flag), _stream()), "pnerf_geometry_canvas")
+    if own:
+        check_canvas_flag(flag)
+    return flag
+
+
+def canvas_flag(device):
+    """the zeroed device word geometry_canvas reports a pixel outside the image in"""
+    return torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def check_canvas_flag(flag):
+    """reads a geometry_canvas flag back (one host read) and raises what the library stored there"""
+    L.check(int(flag.cpu()[0]), "pnerf_geometry_canvas (a pixel_idx outside the canvas)")
+
+
 # ------------------------------------------------------------------------------------------ profiling
 def mfma_rate_tflops(mode=2, ms_target=60.0, device=None):
     """TFLOP/s of register-resident v_mfma_f32_32x32x16_f16 on the whole chip (pnerf_debug_mfma_rate; mode 0 zero operands, 1 one constant,
