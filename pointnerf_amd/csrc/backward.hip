@@ -142,13 +142,14 @@ __device__ __forceinline__ void pn_copy_out_kmajor_hs(const char *X, const PnRow
 // scale S_i of their own sample (pn_sample_scale).  The LeakyReLU masks are the forward's sign words (c1, c2) and the saved fp32 c3; d c1..d c3 leave
 // k-major as one f16 plane at the CALL's scale S (rows x S / S_i) for the weight-gradient GEMMs of these layers, d f as fp32 rows (x 1 / S_i) for
 // k_agg_backward.
-// LDS: the tile, d raw [64][4] (slot 3: S_i), the rows' scale records, and the workgroup's running sums of d Wc4 [3][128], d bc3, d bc2, d bc1 [128] (LDS float adds:
-// kept in registers they are 45 loop-carried values per thread next to the GEMM's working set)
+// LDS: the tile, d raw [64][4] (slot 3: S_i), the rows' scale records, and the running sums of d Wc4 [3][128], d bc3, d bc2, d bc1 [128], one set per wave (plain LDS
+// adds by the address's one owner lane; kept in registers they are 45 loop-carried values per thread next to the GEMM's working set)
 // The tile holds 128 columns at most (d c3, d c2, d c1): its rows are 272 bytes apart (68 dwords = 4 mod 64 banks: the GEMM's 16-byte fragment
 // reads of 16 consecutive rows are conflict-free), 35 KB for both planes instead of the 76 KB of the 296-column tile -- THREE workgroups per
 // CU instead of two (the kernel is a chain of short phases with 3.5 us of MFMA work per tile: what it lacks is waves to overlap them).
 constexpr int CB_XRS = 2 * PN_HC + 16, CB_XPL = PN_CTILE * CB_XRS, CB_XBYTES = 2 * CB_XPL;
-constexpr int CB_DRAW = CB_XBYTES, CB_GACC = CB_DRAW + PN_CTILE * 4 * 4, CB_W4 = CB_GACC + 6 * PN_HC * 4, CB_RSC = CB_W4 + 3 * PN_HC * 4, CB_BYTES = CB_RSC + PN_RSC_BYTES;
+constexpr int CB_GSUMS = 6 * PN_HC;             // one wave's running sums: d Wc4 [3][128] | d bc3 | d bc2 | d bc1 [128]
+constexpr int CB_DRAW = CB_XBYTES, CB_GACC = CB_DRAW + PN_CTILE * 4 * 4, CB_W4 = CB_GACC + 4 * CB_GSUMS * 4, CB_RSC = CB_W4 + 3 * PN_HC * 4, CB_BYTES = CB_RSC + PN_RSC_BYTES;
 static_assert(3 * CB_BYTES <= 160 * 1024, "three colour workgroups must fit the 160 KB LDS");
 
 // d(pre-activation) = acc * LeakyReLU' (sign bits of the forward's pre-activations, same lane -> element map): two planes
@@ -166,22 +167,27 @@ __device__ __forceinline__ void cb_epilogue(const f32x16 (&acc)[2][2], unsigned 
         }
 }
 // column sums of the tile's first 128 columns (the bias gradient of the layer whose d(pre-activation) the tile holds), every row brought to the
-// call's scale first (x S / S_i): thread -> 8 columns x 4 rows
+// call's scale first (x S / S_i).  Wave w takes rows 16 w .. + 15, a lane the column pair of one dword: every address of the WAVE'S OWN running
+// sums (gsum) has one owner, so the sums are plain LDS adds in a fixed order (they were 16 threads' float atomics per address)
 __device__ __forceinline__ void cb_bias_sums(const char *X, const PnRowScale &rs, int tid, float *__restrict__ gsum) {
-    const int c0 = 8 * (tid & 15), r0 = 4 * (tid >> 4);
-    float gb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const int cp = tid & 63, r0 = 16 * (tid >> 6);
+    float g0 = 0.f, g1 = 0.f;
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-        const uint4 h = *reinterpret_cast<const uint4 *>(X + (r0 + rr) * CB_XRS + c0 * 2);
-        const uint4 m = *reinterpret_cast<const uint4 *>(X + CB_XPL + (r0 + rr) * CB_XRS + c0 * 2);
+    for (int rr = 0; rr < 16; ++rr) {
+        const unsigned h = *reinterpret_cast<const unsigned *>(X + (r0 + rr) * CB_XRS + cp * 4);
+        const unsigned m = *reinterpret_cast<const unsigned *>(X + CB_XPL + (r0 + rr) * CB_XRS + cp * 4);
         const float f = rs.to_call(r0 + rr);
-        gb[0] = pn_fma2_lo(h.x, m.x, f, gb[0]); gb[1] = pn_fma2_hi(h.x, m.x, f, gb[1]);
-        gb[2] = pn_fma2_lo(h.y, m.y, f, gb[2]); gb[3] = pn_fma2_hi(h.y, m.y, f, gb[3]);
-        gb[4] = pn_fma2_lo(h.z, m.z, f, gb[4]); gb[5] = pn_fma2_hi(h.z, m.z, f, gb[5]);
-        gb[6] = pn_fma2_lo(h.w, m.w, f, gb[6]); gb[7] = pn_fma2_hi(h.w, m.w, f, gb[7]);
+        g0 = pn_fma2_lo(h, m, f, g0); g1 = pn_fma2_hi(h, m, f, g1);
     }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) atomicAdd(gsum + c0 + i, gb[i]);
+    float2 *d = reinterpret_cast<float2 *>(gsum) + cp;
+    const float2 t = *d;
+    *d = make_float2(t.x + g0, t.y + g1);
+}
+
+__device__ __forceinline__ void cb_add4(float *__restrict__ d, const float (&v)[4]) {      // d[0 .. 3] += v: the caller owns the four addresses
+    float4 *p = reinterpret_cast<float4 *>(d);
+    const float4 t = *p;
+    *p = make_float4(t.x + v[0], t.y + v[1], t.z + v[2], t.w + v[3]);
 }
 
 // WG2: the two-plane weight-gradient mode (pnerf_set_wgrad_planes(2)): the residual plane of every d c tile leaves as well
@@ -197,8 +203,12 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
     float S, invS;
     pn_scale_from_bits(a.sv.gscale[0], S, invS);
     if (blockIdx.x == 0 && threadIdx.x == 0) a.sv.cls_info[PN_CI_CTILES] = (Ns + PN_CTILE - 1) / PN_CTILE;       // for the weight-gradient GEMMs
-    float *gacc = reinterpret_cast<float *>(smem_cb + CB_GACC);          // [3][128] d Wc4 | d bc3 | d bc2 (x S) | d bc1 (x S)
-    for (int i = threadIdx.x; i < 6 * PN_HC; i += 256) gacc[i] = 0.f;
+    // running sums, one set per wave: [3][128] d Wc4 | d bc3 | d bc2 (x S) | d bc1 (x S).  A wave adds a tile's column sums to its own set with
+    // plain LDS adds, one owner lane per address and a fixed order (they were 6 144 LDS float atomics per tile on one shared set); the four sets
+    // meet at the end
+    float *gacc = reinterpret_cast<float *>(smem_cb + CB_GACC);
+    for (int i = threadIdx.x; i < 4 * CB_GSUMS; i += 256) gacc[i] = 0.f;
+    float *gaccw = gacc + (threadIdx.x >> 6) * CB_GSUMS;
     float gb4x = 0.f, gb4y = 0.f, gb4z = 0.f;
     // d(pre-sigmoid colour) of this thread's row (threads 0 .. 63) is formed from two dependent gathers (sample id -> decoded / its gradient):
     // requested one tile ahead (the id at the top of the previous tile, the six values behind its first GEMM), so that no tile starts with two
@@ -226,6 +236,12 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const long long grow0 = tile * PN_CTILE;
+        // the tile's saved forward values (the thread's 8 x 4 of c3, its two sign words) are requested here, in front of the d raw phase, not
+        // where they are used: 0.650 -> 0.627 ms (profiles/streaming_kernels.json), 160 VGPRs
+        float4 c3v[8];
+#pragma unroll
+        for (int rr = 0; rr < 8; ++rr) c3v[rr] = *reinterpret_cast<const float4 *>(a.sv.c3 + (grow0 + 8 * (tid >> 5) + rr) * PN_HC + 4 * (tid & 31));
+        const unsigned mw2 = a.sv.cmask[(tile * 2 + 1) * 256 + tid], mw1 = a.sv.cmask[(tile * 2 + 0) * 256 + tid];
         PN_LDS_BARRIER();
         if (tid < PN_CTILE) {
             float d0 = 0.f, d1 = 0.f, d2 = 0.f, Si = S, invSi = invS;
@@ -241,10 +257,9 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         }
         const long long si_next = row_sample(tile + gridDim.x);
         PN_LDS_BARRIER();
-        // ---- d c3 = (d raw @ Wc4) * lrelu'(c3); d Wc4, d bc4, d bc3 accumulate in registers
+        // ---- d c3 = (d raw @ Wc4) * lrelu'(c3); the tile's d Wc4 and d bc3 go to the wave's running sums in LDS (d bc4: the row threads' registers, above)
         {
             const int c4 = tid & 31, rg = tid >> 5;
-            float4 c3v[8];
             float w4[3][4], gw4[3][4], gb3[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -253,8 +268,6 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) gw4[k][i] = 0.f;
             }
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) c3v[rr] = *reinterpret_cast<const float4 *>(a.sv.c3 + (grow0 + 8 * rg + rr) * PN_HC + 4 * c4);
 #pragma unroll
             for (int rr = 0; rr < 8; ++rr) {
                 const int row = 8 * rg + rr;
@@ -269,11 +282,17 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
                 }
                 pn_x_store4<true, CB_XRS, CB_XPL>(X, row, 4 * c4, u[0] * d.w, u[1] * d.w, u[2] * d.w, u[3] * d.w);
             }
+            // the wave's two row groups share their columns lane l <-> l + 32: one exchange, then the lower half adds to the wave's sums
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) atomicAdd(gacc + k * PN_HC + 4 * c4 + i, gw4[k][i]);
-                atomicAdd(gacc + 3 * PN_HC + 4 * c4 + i, gb3[i]);
+                for (int k = 0; k < 3; ++k) gw4[k][i] += __shfl_xor(gw4[k][i], 32, 64);
+                gb3[i] += __shfl_xor(gb3[i], 32, 64);
+            }
+            if (lane < 32) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) cb_add4(gaccw + k * PN_HC + 4 * c4, gw4[k]);
+                cb_add4(gaccw + 3 * PN_HC + 4 * c4, gb3);
             }
         }
         // (round 4: the first weight chunks of each GEMM are requested in front of the barrier that precedes it: see k_color_forward)
@@ -283,7 +302,6 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         // ---- d c2 = (d c3 @ Wc3) * lrelu'(c2)
         pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X, rs, a.sv.dc3k, tile * 8, tid);
         if (WG2) pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X + CB_XPL, rs, a.sv.dc3m, tile * 8, tid);
-        const unsigned mw2 = a.sv.cmask[(tile * 2 + 1) * 256 + tid], mw1 = a.sv.cmask[(tile * 2 + 0) * 256 + tid];
         pn_acc_zero(acc);
         pn_gemm_f16x3_run<8, 4, 1, 4, 3, CB_XRS, CB_XPL>(X, WD3, lane, acc);
         row_values(si_next);                              // (the next tile's six values: consumed at the top of the next iteration)
@@ -293,7 +311,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         PnGemmW<8, 4, 1, 4, 3> WD2;
         WD2.prefetch(reinterpret_cast<const uint4 *>(img + PKH_DC2), wave, lane);
         PN_LDS_BARRIER();
-        cb_bias_sums(X, rs, tid, gacc + 4 * PN_HC);
+        cb_bias_sums(X, rs, tid, gaccw + 4 * PN_HC);
         // ---- d c1 = (d c2 @ Wc2) * lrelu'(c1)
         pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X, rs, a.sv.dc2k, tile * 8, tid);
         if (WG2) pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X + CB_XPL, rs, a.sv.dc2m, tile * 8, tid);
@@ -304,7 +322,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         PnGemmW<8, 8, 2, 1, 3> WD1;
         WD1.prefetch(reinterpret_cast<const uint4 *>(img + PKH_DC1), 2 * wave, lane);
         PN_LDS_BARRIER();
-        cb_bias_sums(X, rs, tid, gacc + 5 * PN_HC);
+        cb_bias_sums(X, rs, tid, gaccw + 5 * PN_HC);
         pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X, rs, a.sv.dc1k, tile * 8, tid);
         if (WG2) pn_copy_out_kmajor_hs<PN_HC, CB_XRS>(X + CB_XPL, rs, a.sv.dc1m, tile * 8, tid);
         // ---- d f = d c1 @ Wc1[:, :256]
@@ -325,11 +343,12 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
     PN_LDS_BARRIER();
     {
         const int tid = threadIdx.x;
-        for (int i = tid; i < 3 * PN_HC; i += 256) atomicAdd(&a.gparams[PO_WC4 + i], gacc[i]);
+        auto total = [&](int i) { return (gacc[i] + gacc[CB_GSUMS + i]) + (gacc[2 * CB_GSUMS + i] + gacc[3 * CB_GSUMS + i]); };      // the four waves' sets
+        for (int i = tid; i < 3 * PN_HC; i += 256) atomicAdd(&a.gparams[PO_WC4 + i], total(i));
         if (tid < PN_HC) {
-            atomicAdd(&a.gparams[PO_BC3 + tid], gacc[3 * PN_HC + tid]);
-            atomicAdd(&a.gparams[PO_BC2 + tid], gacc[4 * PN_HC + tid] * invS);
-            atomicAdd(&a.gparams[PO_BC1 + tid], gacc[5 * PN_HC + tid] * invS);
+            atomicAdd(&a.gparams[PO_BC3 + tid], total(3 * PN_HC + tid));
+            atomicAdd(&a.gparams[PO_BC2 + tid], total(4 * PN_HC + tid) * invS);
+            atomicAdd(&a.gparams[PO_BC1 + tid], total(5 * PN_HC + tid) * invS);
         }
         if (tid < PN_CTILE) {                              // d bc4: the row threads' partial column sums (wave 0)
 #pragma unroll
@@ -918,11 +937,23 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
 #else
 #define PN_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
 #endif
+// Cache policy of the operand streams (the aux operand of global_load_lds: 0 = default, 2 = nt).  Every dY / X byte of these kernels is read
+// exactly once per step, so the lines need not stay in L2 behind the copy: non-temporal.  (Not the embedding gather of k_wgrad_x0: a point's
+// row is read by every sample that uses it.)
+#ifndef PN_WG_AUX
+#define PN_WG_AUX 2
+#endif
+#ifndef PN_WX_AUX
+#define PN_WX_AUX 2
+#endif
 #ifndef PN_WG_RS
 #define PN_WG_RS 32             // rows per stage of the aggregator layers' weight-gradient GEMMs (dev A/B: -DPN_WG_RS=16 -DPN_WG_NST=4 is round 2's)
 #endif
 #ifndef PN_WG_NST
 #define PN_WG_NST 4
+#endif
+#ifndef PN_WGC_RS
+#define PN_WGC_RS 32            // rows per stage of the colour layers' (one-plane) weight-gradient GEMMs
 #endif
 template <int N> __device__ __forceinline__ void pn_wait_vm_stages(int stages) {       // wait until at most `stages` x N of this wave's loads are outstanding
     if (stages >= 3) PN_WAIT_VMCNT(3 * N);
@@ -985,7 +1016,7 @@ __global__ __launch_bounds__(512) void k_wgrad_f16(const uint4 *__restrict__ A, 
             else if (u0 < HALF) src = B + rg * NFB + (u0 - AU);
             else if (u0 < HALF + AU) src = Am + rg * MF + (u0 - HALF);
             else src = Bm + rg * NFB + (u0 - HALF - AU);
-            __builtin_amdgcn_global_load_lds(src + lane, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src + lane, (__attribute__((address_space(3))) void *)dst, 16, 0, PN_WG_AUX);
         }
     };
     pn_h8 ones = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1110,8 +1141,9 @@ struct WgLayer {
 template <int NFB, int MF, int RS, int NST, bool TWO>
 int launch_wgrad_f16(const WgLayer &L, float *partial, const unsigned *gscale, float *grad, hipStream_t s) {
     int chunks = WG_CHUNKS;
-    const long long tiles = L.rows_max / PN_TILE;
-    if (tiles < chunks) chunks = (int)(tiles > 0 ? tiles : 1);
+    // one workgroup per tile at most; the colour layers (MF == 128): no more workgroups than have a ring's worth of stages each
+    const long long most = MF == PN_HC ? L.rows_max / ((long long)RS * NST) : L.rows_max / PN_TILE;
+    if (most < chunks) chunks = (int)(most > 0 ? most : 1);
     if ((size_t)chunks * 256 * 288 > PARTIAL_FLOATS) return PNERF_E_WS;
     if (TWO && (!L.dym || !L.xm)) return PNERF_E_INVAL;
     constexpr size_t lds = ((size_t)NST * (TWO ? 2 : 1) * (RS / 8) * (MF + NFB) + 64) * 16;   // the stages [dY | X] (TWO: both planes of each) + the pad slot
@@ -1124,17 +1156,18 @@ int launch_wgrad_f16(const WgLayer &L, float *partial, const unsigned *gscale, f
     PN_CHECK_LAUNCH();
     return 0;
 }
-// the instance for a layer's shape.  One plane: PN_WG_RS-row stages for the aggregator layers, 16-row stages x 4 for the colour layers.  Two planes:
+// the instance for a layer's shape.  One plane: PN_WG_RS-row stages for the aggregator layers, PN_WGC_RS-row stages x 4 for the colour layers (32 rows
+// since the streaming-kernel round: 0.06 ms of the three launches' 0.47 against 16-row stages, the rendezvous per row halved as for the aggregator layers).  Two planes:
 // dW = dYh^T Xh + dYh^T Xm + dYm^T Xh in ONE pass per layer (a stage holds both planes of both operands; round 4 ran the one-plane kernel three
 // times per layer), 16-row stages everywhere: four planes of 32 rows would not leave four ring slots.
 template <bool TWO>
 int launch_wgrad_layer(const WgLayer &L, float *partial, const unsigned *gscale, float *grad, hipStream_t s) {
-    constexpr int RS = TWO ? 16 : PN_WG_RS, NST = TWO ? 4 : PN_WG_NST;
+    constexpr int RS = TWO ? 16 : PN_WG_RS, NST = TWO ? 4 : PN_WG_NST, RSC = TWO ? 16 : PN_WGC_RS;
     switch (L.shape) {
         case WG_288x256: return launch_wgrad_f16<PN_NF1, PN_H, RS, NST, TWO>(L, partial, gscale, grad, s);
         case WG_256x256: return launch_wgrad_f16<PN_H, PN_H, RS, NST, TWO>(L, partial, gscale, grad, s);
-        case WG_288x128: return launch_wgrad_f16<PN_NF1, PN_HC, 16, 4, TWO>(L, partial, gscale, grad, s);
-        default: return launch_wgrad_f16<PN_HC, PN_HC, 16, 4, TWO>(L, partial, gscale, grad, s);
+        case WG_288x128: return launch_wgrad_f16<PN_NF1, PN_HC, RSC, 4, TWO>(L, partial, gscale, grad, s);
+        default: return launch_wgrad_f16<PN_HC, PN_HC, RSC, 4, TWO>(L, partial, gscale, grad, s);
     }
 }
 
@@ -1220,12 +1253,12 @@ __global__ __launch_bounds__(512) void k_wgrad_x0(const uint4 *__restrict__ A, W
             const int piece = wave + 8 * i;
             const uint4 *src = A + (ok ? stage_rg(s) * MF + 64 * piece : 0) + lane;
             const uint4 *dst = smem_x + (ok ? (s % WX_NST) * WX_AU + 64 * piece : WX_OFF_PAD);
-            __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
+            __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, PN_WX_AUX);
         }
         const bool okt = ok && wave < WX_RG;            // piece rg = 64 units of the saved last-64-column plane
         const uint4 *src = g.x0t + (okt ? (stage_rg(s) + wave) * 64 : 0) + lane;
         const uint4 *dst = smem_x + (okt ? WX_OFF_T + (s % WX_NST) * WX_TU + wave * 64 : WX_OFF_PAD);
-        __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, PN_WX_AUX);
     };
     auto issue_second = [&](int s_rm, int s_g) {        // ONE instruction: metadata (wave 0), embedding rows (waves 1 .. RG), pad (the rest)
         if (wave == 0) {                                // the stage's (sample, point, ., .) records, one per row
@@ -1308,8 +1341,8 @@ __global__ __launch_bounds__(512) void k_wgrad_x0(const uint4 *__restrict__ A, W
             if (s < n_main) {
 #pragma unroll
                 for (int i = 0; i < WX_NA; ++i)
-                    __builtin_amdgcn_global_load_lds(pa + 512 * i, (__attribute__((address_space(3))) void *)(smem_x + ia * WX_AU + 64 * (wave + 8 * i)), 16, 0, 0);
-                if (wave < WX_RG) __builtin_amdgcn_global_load_lds(pt, (__attribute__((address_space(3))) void *)(smem_x + WX_OFF_T + ia * WX_TU + wave * 64), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds(pa + 512 * i, (__attribute__((address_space(3))) void *)(smem_x + ia * WX_AU + 64 * (wave + 8 * i)), 16, 0, PN_WX_AUX);
+                if (wave < WX_RG) __builtin_amdgcn_global_load_lds(pt, (__attribute__((address_space(3))) void *)(smem_x + WX_OFF_T + ia * WX_TU + wave * 64), 16, 0, PN_WX_AUX);
                 else __builtin_amdgcn_global_load_lds(A + lane, (__attribute__((address_space(3))) void *)(smem_x + WX_OFF_PAD), 16, 0, 0);
                 if (wave == 0) {
                     if (lane < WX_RS) __builtin_amdgcn_global_load_lds(prm, (__attribute__((address_space(3))) void *)(smem_x + WX_OFF_RM + irm * WX_RS), 16, 0, 0);
@@ -1426,7 +1459,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     if (xg && (!ax.xyz || !ax.sample_loc)) return PNERF_E_INVAL;
     const int ncu = pn_cu_count();
     if (!ncu) return PNERF_E_LAUNCH;
-    const int grid_c = pn_capped_grid((n_valid + PN_CTILE - 1) / PN_CTILE, 3LL * ncu);       // 40 KB of LDS: three workgroups per CU
+    const int grid_c = pn_capped_grid((n_valid + PN_CTILE - 1) / PN_CTILE, 3LL * ncu);       // 50.8 KB of LDS: three workgroups per CU
     const size_t lds_c = CB_BYTES, lds_a = xg ? BL_BYTES_X : BL_BYTES;
     const bool wg2 = sv.wg2 != 0;                      // two-plane weight-gradient mode (the forward of this step ran in it: same process-wide setting)
     if (wg2) x0_saved = true;
