@@ -306,6 +306,12 @@ int pnerf_set_cross_terms_where(int mask);
 /* The four settings above as they are now, without changing them: out = {inference products, weight-gradient planes, cross-term bits, the
  * cross-term mask AS STORED} (the mask takes effect only while the cross-term bits are 8).  0, or PNERF_E_INVAL for a null pointer. */
 int pnerf_get_arithmetic(int32_t out[4]);
+/* Tests only: caps the grid of the aggregator's tile kernels and of the colour kernels at max_workgroups (0, the default: as many workgroups
+ * as stay resident, two or three per CU).  Which workgroup runs a tile does not change a forward's results and changes gradients only by the
+ * order of their atomic additions; a small grid reaches the edges of the kernels' tile claim with a handful of tiles.  Returns the previous
+ * cap, or PNERF_E_INVAL for a negative one.  Process-wide and unsynchronised: every launcher reads it, so it must not be changed while another
+ * thread may be inside a pnerf_render_* / pnerf_agg_* call. */
+int pnerf_debug_set_tile_grid(int max_workgroups);
 
 /* Backward of pnerf_render_forward for dL/d(ray_color) = d_grad_ray_color [R,3]:
  * accumulates dL/d(MLP params) into d_grad_params (flat, pnerf_mlp_layout order) and

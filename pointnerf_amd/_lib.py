@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1003                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1004                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
@@ -117,6 +117,7 @@ PROTOTYPES = {
     "pnerf_set_cross_terms": (c_int, [c_int]),
     "pnerf_set_cross_terms_where": (c_int, [c_int]),
     "pnerf_get_arithmetic": (c_int, [ctypes.POINTER(ctypes.c_int32)]),
+    "pnerf_debug_set_tile_grid": (c_int, [c_int]),
     "pnerf_compact_workspace_bytes": (c_size_t, [c_i64]),
     "pnerf_touched_flags": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "pnerf_compact_valid": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

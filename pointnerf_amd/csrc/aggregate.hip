@@ -317,7 +317,7 @@ size_t pn_saved_walk(void *base, long long n_valid, int K, PnSaved &s) {
     s.h4r = cv.take<uint4>((size_t)s.rows * 32 * 2);
     s.arow = cv.take<float>((size_t)s.rows); s.rmeta = cv.take<int4>((size_t)s.rows);
     s.lmask = cv.take<unsigned>((size_t)tiles * 3 * 512);
-    s.gscale = cv.take<unsigned>(4);
+    s.gscale = cv.take<unsigned>(PN_GS_WORDS);
     s.fs = cv.take<float>((size_t)s.samples * PN_H); s.dfs = cv.take<float>((size_t)s.samples * PN_H);
     s.c3 = cv.take<float>((size_t)s.samples * PN_HC);
     cplanes(s.xck, s.c1k, s.c2k, s.dc1k, s.dc2k, s.dc3k);
@@ -471,7 +471,7 @@ namespace {
 //   exb   [64][8] f32       layer-3 extras of the tile's rows until they move next to h2
 //   w5s   [256] f32         alpha head weights
 //   rowf  wraw, wrow, wnrm [64] f32, sidx [64] int
-constexpr int FL_EX = PN_XBYTES, FL_W5 = FL_EX + PN_TILE * 8 * 4, FL_ROW = FL_W5 + PN_H * 4, FL_BYTES = FL_ROW + 4 * PN_TILE * 4;
+constexpr int FL_EX = PN_XBYTES, FL_W5 = FL_EX + PN_TILE * 8 * 4, FL_ROW = FL_W5 + PN_H * 4, FL_CLAIM = FL_ROW + 4 * PN_TILE * 4 /* the claimed tile: one word */, FL_BYTES = FL_CLAIM + 16;
 static_assert(2 * FL_BYTES <= 160 * 1024, "two forward workgroups must fit the 160 KB LDS");
 
 struct FGather {               // what a thread holds of one tile row (4 threads per row, q = thread in row)
@@ -764,6 +764,7 @@ __device__ __forceinline__ void f_tail(const FwdArgs &a, const char *X, const fl
 
 #ifdef PN_PHASE_TRACE
 PN_TR_DECL(pn_trace_fwd);
+PN_TR_SPAN_DECL(pn_span_fwd);
 #endif
 // WG2: the two-plane weight-gradient mode (pnerf_set_wgrad_planes(2)): every saved GEMM operand also leaves its residual plane, X0 whole
 // NP = 4: the mixed format of mixq.h (f16 h.h + e4m3 cross terms: the default since round 6); NP = 3 / 2: f16x3.h's three / two f16 products
@@ -799,19 +800,23 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
     const char *img = reinterpret_cast<const char *>(a.packed);
     if (tid0 < PN_H) w5s[tid0] = P[PO_W5 + tid0];
     const float b5 = P[PO_B5];
-    // tiles of a workgroup: blockIdx.x, blockIdx.x + gridDim.x, ... (the chip works on one moving window of the saved area; one contiguous
-    // run of tiles per workgroup measured the same, 12.85 against 12.90 ms)
-    const long long stride = gridDim.x, tile_first = blockIdx.x, tile_last = ntiles;
-    if (tile_first >= tile_last) return;
+    // tiles of a workgroup: blockIdx.x + j * gridDim.x for j < PN_CLAIM_STATIC_FWD (what the index pipeline below looks ahead), then whatever it
+    // claims (mlp_common.h: dynamic tile claim) -- in ascending order, so the chip still works on one moving window of the saved area (one
+    // contiguous run of tiles per workgroup measured the same, 12.85 against 12.90 ms).  t0 .. t2: this tile and the next two, uniform
+    const int tile_last = (int)ntiles, grid = gridDim.x;
+    int t0 = blockIdx.x, t1 = t0 + grid, t2 = t1 + grid;
+    if (t0 >= tile_last) return;
+    int *claim_ctr = a.sv.cls_info + PN_CI_CLAIM + a.cls, *claim_w = reinterpret_cast<int *>(smem_f + FL_CLAIM);
+    int nclaim = 0;                                    // claim sequence number of the tile the NEXT iteration learns (its t3)
 
     // index pipeline of this thread's row (4 threads per tile row): (si0, p0) current tile, (si1, p1) next, si2 the one after
-    long long tile = tile_first;
+    long long tile = t0;
     int si0, si1, si2, p0, p1;
     FGather G;
     {
         const int row = tid0 / PN_TPR, q = tid0 % PN_TPR, k = row - pn_row_div(row, kinv) * K;
-        si0 = f_sample_of(a, tile, row, Ns, kinv); si1 = tile + stride < tile_last ? f_sample_of(a, tile + stride, row, Ns, kinv) : -1;
-        si2 = tile + 2 * stride < tile_last ? f_sample_of(a, tile + 2 * stride, row, Ns, kinv) : -1;
+        si0 = f_sample_of(a, tile, row, Ns, kinv); si1 = t1 < tile_last ? f_sample_of(a, t1, row, Ns, kinv) : -1;
+        si2 = t2 < tile_last ? f_sample_of(a, t2, row, Ns, kinv) : -1;
         p0 = si0 >= 0 ? a.pidx[(long long)si0 * a.Kstride + k] : -1;
         p1 = si1 >= 0 ? a.pidx[(long long)si1 * a.Kstride + k] : -1;
         f_gather<PERS, FRAMES>(a, G, si0, p0, q, frames);
@@ -819,8 +824,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
 
     f32x16 acc[PN_NFB][2];
     PN_TR_ITER_DECL;
-    for (; tile < tile_last; tile += stride) {
+    for (bool first = true; t0 < tile_last; first = false) {
         PN_TR_ITER_NEXT;
+        tile = t0;
         // thread-index-derived offsets are recomputed per tile: hoisted out of the loop they become hundreds of loop-carried
         // registers (every LDS / bias / image address of every unrolled store) and spill
         int tid = threadIdx.x;
@@ -829,7 +835,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         const int row = tid / PN_TPR, q = tid % PN_TPR, k = row - pn_row_div(row, kinv) * K;
         const long long gtile = tb + tile;               // tile index inside the saved area
         PN_LDS_BARRIER();                                 // the previous tile's readers are done with X and the row arrays
-        PN_TR(pn_trace_fwd, 0); PN_TR_HWID(pn_trace_fwd);
+        PN_TR(pn_trace_fwd, 0); PN_TR_HWID(pn_trace_fwd); PN_TR_SPAN(pn_span_fwd, a.cls, 0);
         f_build<PERS, MIX, FRAMES>(a, G, X, exb, wraw, sidx, si0, p0, row, q);
         // Round 4: what the next GEMM needs from GLOBAL memory -- its bias (the accumulators' initial value) and its first weight-fragment
         // chunks -- is requested in front of the barrier that precedes it, not behind: neither depends on LDS, and the L2 round trip
@@ -925,10 +931,17 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         PN_TR(pn_trace_fwd, 12);
         // the next tile's point data and the indices of the two after it: requested here, consumed at the top of the next
         // iteration -- their HBM latency passes under the element-wise tail of this tile (nothing of this tile waits for memory any more)
+        // the tile three ahead: static in the first iteration, else the claim the previous iteration left in LDS (barriers lie between its write
+        // at the end of that iteration, this read, and the next write).  This iteration's own claim is requested here, in front of the loads below,
+        // and lands in LDS at the end of the iteration: its round trip passes under the layer-4 epilogue and the tail
+        const int t3 = first ? t2 + grid : pn_claim_tile(PN_CLAIM_STATIC_FWD, grid, __builtin_amdgcn_readfirstlane(*claim_w), nclaim - 1);
+        const bool claims = nclaim % PN_CLAIM_TILES == 0;
+        int claimed = 0;
+        if (tid == 0 && claims) claimed = atomicAdd(claim_ctr, 1);
         const int si_next = si1, p_next = p1;
-        if (tile + stride < tile_last) f_gather<PERS, FRAMES>(a, G, si1, p1, q, frames);
+        if (t1 < tile_last) f_gather<PERS, FRAMES>(a, G, si1, p1, q, frames);
         const int p2 = si2 >= 0 ? a.pidx[(long long)si2 * a.Kstride + k] : -1;
-        const int si3 = tile + 3 * stride < tile_last ? f_sample_of(a, tile + 3 * stride, row, Ns, kinv) : -1;
+        const int si3 = t3 < tile_last ? f_sample_of(a, t3, row, Ns, kinv) : -1;
         PN_LDS_BARRIER();
         PN_TR(pn_trace_fwd, 13);
         f_epilogue<false>(acc, X, wave, lane, mask);
@@ -975,7 +988,9 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_forward(typename Fwd
         }
         }
         si0 = si_next; p0 = p_next; si1 = si2; p1 = p2; si2 = si3;
-        PN_TR(pn_trace_fwd, 16);
+        if (tid == 0 && claims) *claim_w = claimed;
+        t0 = t1; t1 = t2; t2 = t3; ++nclaim;
+        PN_TR(pn_trace_fwd, 16); PN_TR_SPAN(pn_span_fwd, a.cls, 1);
     }
 }
 
@@ -1164,6 +1179,15 @@ extern "C" int pnerf_set_inference_products(int n) { return pn_arith_set(&PnArit
 extern "C" int pnerf_set_wgrad_planes(int n) { return pn_arith_set(&PnArith::wgrad_planes, n, n == 1 || n == 2); }
 extern "C" int pnerf_set_cross_terms(int bits) { return pn_arith_set(&PnArith::cross_terms, bits, bits == 8 || bits == 16); }
 extern "C" int pnerf_set_cross_terms_where(int mask) { return pn_arith_set(&PnArith::mix_where, mask, mask >= 0 && mask <= 7); }
+// the grid of the tile and colour kernels (tests: a handful of workgroups reaches every edge of the tile claim with a handful of tiles)
+static int pn_tile_grid_cap = 0;
+int pn_tile_grid(long long tiles, long long dflt) { return pn_capped_grid(tiles, pn_tile_grid_cap > 0 && pn_tile_grid_cap < dflt ? pn_tile_grid_cap : dflt); }
+extern "C" int pnerf_debug_set_tile_grid(int max_workgroups) {
+    if (max_workgroups < 0) return PNERF_E_INVAL;
+    const int old = pn_tile_grid_cap;
+    pn_tile_grid_cap = max_workgroups;
+    return old;
+}
 extern "C" int pnerf_get_arithmetic(int32_t out[4]) {
     if (!out) return PNERF_E_INVAL;
     const PnArith a = pn_arith();
@@ -1192,7 +1216,7 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
     if (frames && train) return PNERF_E_INVAL;            // per-point frames are render-only (include/pnerf.h: pnerf_points.frames)
     const int ncu = pn_cu_count();
     if (!ncu) return PNERF_E_LAUNCH;
-    const int grid_c = pn_capped_grid((cap_samples + PN_CTILE - 1) / PN_CTILE, 2LL * ncu);       // two workgroups per CU
+    const int grid_c = pn_tile_grid((cap_samples + PN_CTILE - 1) / PN_CTILE, 2LL * ncu);       // two workgroups per CU
     const size_t lds_a = FL_BYTES, lds_c = CL_BYTES;
     const bool pers = st.xyz_pers != nullptr;
     const bool np2 = !train && ar.products == 2;      // inference with the weights' high plane only (f16x3.h: NP)
@@ -1221,7 +1245,7 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
         PnProfScope prof(PNK_AGG_FWD, s);
         for (int j = 0; j < ncls; ++j) {            // class sizes are only known on the device: the grid covers the worst case, surplus workgroups return at once
             a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
-            const int grid_a = pn_capped_grid((cap_samples + a.TS - 1) / a.TS, 2LL * ncu);     // two workgroups per CU
+            const int grid_a = pn_tile_grid((cap_samples + a.TS - 1) / a.TS, 2LL * ncu);     // two workgroups per CU
             if (frames) { FwdArgsF af; static_cast<FwdArgs &>(af) = a; af.frames = pts->frames; hipLaunchKernelGGL(kfnf, dim3(grid_a), dim3(PN_NTHR), lds_a, s, af); }
             else hipLaunchKernelGGL(kfn, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
         }
@@ -1239,5 +1263,8 @@ int pn_agg_forward_launch(const pnerf_camera *cam, const pnerf_points *pts, cons
 #ifdef PN_PHASE_TRACE
 extern "C" int pnerf_debug_trace_fwd(void *host, size_t bytes) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(pn_trace_fwd), bytes < sizeof(pn_trace_fwd) ? bytes : sizeof(pn_trace_fwd)) == hipSuccess ? 0 : -1;
+}
+extern "C" int pnerf_debug_span_fwd(void *host, size_t bytes) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pn_span_fwd), bytes < sizeof(pn_span_fwd) ? bytes : sizeof(pn_span_fwd)) == hipSuccess ? 0 : -1;
 }
 #endif

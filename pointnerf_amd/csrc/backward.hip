@@ -366,7 +366,7 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
 //   -> layer-3 extras (d colour, d dir) as a ninth feature block, K split over the four waves
 //   -> d X0 (224 columns: the embedding and its encoding) as fp32 in LDS -> PE chain rule -> atomics into the touched points.
 // Bias gradients are not formed here: they are the ones-column of the weight-gradient GEMMs.
-constexpr int BL_ROW = PN_XBYTES, BL_RSC = BL_ROW + 10 * PN_TILE * 4, BL_W5 = BL_RSC + PN_RSC_BYTES, BL_BYTES = BL_W5 + PN_H * 4;
+constexpr int BL_ROW = PN_XBYTES, BL_RSC = BL_ROW + 10 * PN_TILE * 4, BL_W5 = BL_RSC + PN_RSC_BYTES, BL_CLAIM = BL_W5 + PN_H * 4 /* the claimed tile: one word */, BL_BYTES = BL_CLAIM + 16;
 constexpr int LDDX = 228;                      // fp32 row stride of the d X0 tile (over the activation tile's space)
 static_assert(2 * BL_BYTES <= 160 * 1024, "two backward workgroups must fit the 160 KB LDS");
 static_assert(PN_TILE * LDDX * 4 <= PN_XBYTES, "d X0 tile");
@@ -466,7 +466,9 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
                 const float alpha = pn_softplus(x), sg = pn_sigmoid(x);
                 const int rp = prow[r];
                 // w = wn * clamp(conf) with a straight-through clamp (gradiant_clamp, point_aggregators.py:722-724)
-                if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * rs.inv(r) + (a.zo_gs ? PnZeroOne(zo_conf, a.zo_eps).grad(a.zo_gs[0]) : 0.f));
+                float zo_eps = a.zo_eps;
+                asm volatile("" : "+s"(zo_eps));          // (re-read per tile: hoisted, 1 - eps is one more loop-carried register, and that one spilled)
+                if (rp >= 0) atomicAdd(&a.g_conf[rp], (dsg[r] * alpha + dotf) * wnrm[r] * rs.inv(r) + (a.zo_gs ? PnZeroOne(zo_conf, zo_eps).grad(a.zo_gs[0]) : 0.f));
                 if (XG && rp >= 0) gw = dsg[r] * alpha + dotf;
                 dr = dsg[r] * wrow[r] * sg;
             }
@@ -568,6 +570,7 @@ __device__ __forceinline__ void b_xyz_row(const BwdXArgs &a, const float *dxr, c
 
 #ifdef PN_PHASE_TRACE
 PN_TR_DECL(pn_trace_bwd);
+PN_TR_SPAN_DECL(pn_span_bwd);
 #endif
 // MIX: the four input-gradient GEMMs in the mixed format of mixq.h (f16 h.h + e4m3 cross terms; the default since round 6)
 // XYZG (xyz_grad, a.g_xyz): the layer-1 dgrad also forms d X0 columns 224 .. 287 (two more feature blocks, image PKH_D1T / PKM_D1T, on the
@@ -604,7 +607,16 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
     f32x16 acc[PN_NFB][2];
     // row metadata of the tile (threads 0..63: one row each), fetched ONE TILE AHEAD: the d sigma of a row hangs off its sample id, and
     // two dependent HBM round trips at the top of every tile were 4 of the 6 us of the load phase
-    const long long stride = gridDim.x, tile_first = blockIdx.x, tile_last = ntiles;
+    // tiles of a workgroup: blockIdx.x, blockIdx.x + gridDim.x, then whatever it claims (mlp_common.h: dynamic tile claim).  t_cur, t_nxt: uniform
+    // The xyz_grad instances with f16 cross terms or two planes (XYZG && !MIX) are dealt statically, blockIdx.x + j * gridDim.x throughout, in
+    // the loop's earlier form: with the claim's form of the loop their register allocation spills a 16-register tuple inside the tile loop
+    constexpr bool CLAIM = !(XYZG && !MIX);
+    using tile_t = std::conditional_t<CLAIM, int, long long>;
+    const tile_t tile_first = blockIdx.x, tile_last = (tile_t)ntiles, grid = gridDim.x;
+    tile_t t_cur = tile_first;
+    [[maybe_unused]] tile_t t_nxt = t_cur + grid;
+    int nclaim = 0;
+    int *claim_ctr = reinterpret_cast<int *>(a.sv.gscale) + PN_GS_CLAIM + a.cls, *claim_w = reinterpret_cast<int *>(smem_b + BL_CLAIM);
     int4 rm_cur = make_int4(-1, -1, 0, 0);
     float ar_cur = 0.f;
     if (tid0 < PN_TILE && tile_first < tile_last) {
@@ -612,15 +624,16 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         ar_cur = a.sv.arow[(tb + tile_first) * PN_TILE + tid0];
     }
     PN_TR_ITER_DECL;
-    for (long long tile = tile_first; tile < tile_last; tile += stride) {
+    for (; t_cur < tile_last; ++nclaim) {
         PN_TR_ITER_NEXT;
+        const long long tile = t_cur;
         int tid = threadIdx.x;                          // (recomputed per tile: see the forward)
         asm volatile("" : "+v"(tid));
         const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         const int row = tid / PN_TPR, q = tid % PN_TPR;          // the row-wise phases: 4 threads per tile row
         const long long gtile = tb + tile;
         PN_LDS_BARRIER();
-        PN_TR(pn_trace_bwd, 0); PN_TR_HWID(pn_trace_bwd);
+        PN_TR(pn_trace_bwd, 0); PN_TR_HWID(pn_trace_bwd); PN_TR_SPAN(pn_span_bwd, a.cls, 0);
         // ---- load: sign words, d sigma of the rows, the h4 planes (-> LDS before the barrier), the next tile's row metadata: one burst
         unsigned m1[PN_NFB], m2[PN_NFB], m3[PN_NFB];
 #pragma unroll
@@ -646,9 +659,16 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         }
         int4 rm_nxt = make_int4(-1, -1, 0, 0);
         float ar_nxt = 0.f;
-        if (tid < PN_TILE && tile + stride < tile_last) {
-            rm_nxt = a.sv.rmeta[(gtile + stride) * PN_TILE + tid];
-            ar_nxt = a.sv.arow[(gtile + stride) * PN_TILE + tid];
+        if constexpr (CLAIM) {
+            if (tid < PN_TILE && t_nxt < tile_last) {
+                rm_nxt = a.sv.rmeta[(tb + t_nxt) * PN_TILE + tid];
+                ar_nxt = a.sv.arow[(tb + t_nxt) * PN_TILE + tid];
+            }
+        } else {
+            if (tid < PN_TILE && tile + grid < tile_last) {
+                rm_nxt = a.sv.rmeta[(gtile + grid) * PN_TILE + tid];
+                ar_nxt = a.sv.arow[(gtile + grid) * PN_TILE + tid];
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (tid < PN_TILE) {
@@ -679,6 +699,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         rm_cur = rm_nxt; ar_cur = ar_nxt;
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 1);
+        // the claim of the tile after the next: requested here, where few registers are live (not with the burst above), in LDS before the next
+        // barrier and read right behind it; its round trip passes under the front
+        [[maybe_unused]] const bool claims = nclaim % PN_CLAIM_TILES == 0;
+        [[maybe_unused]] int claimed = 0;
+        if constexpr (CLAIM) { if (tid == 0 && claims) claimed = atomicAdd(claim_ctr, 1); }
         const int rp = prow[row];
         float4 e0 = make_float4(0.f, 0.f, 0.f, 0.f), e1 = e0;       // the row's embedding values (for its gradient at the end of the tile)
         if (rp >= 0) {
@@ -697,8 +722,13 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         // (round 4: the first weight-fragment chunks of every GEMM are requested in FRONT of the barrier that precedes it -- see the forward)
         PnTileW<MIX, 0, 8> W4;
         W4.prefetch(img, PKH_D4, PKM_D4, PN_NFB * wave, lane);
+        if constexpr (CLAIM) { if (tid == 0 && claims) *claim_w = claimed; }
         PN_LDS_BARRIER();
         PN_TR(pn_trace_bwd, 3);
+        if constexpr (CLAIM) {
+            t_cur = t_nxt;               // (`tile` and `gtile` stay this tile's)
+            t_nxt = pn_claim_tile(PN_CLAIM_STATIC_BWD, grid, __builtin_amdgcn_readfirstlane(*claim_w), nclaim);
+        }
         // ---- layer 4: dY4 -> d h3
         // (every dY tile is copied out BEHIND its GEMM: stores and loads of a wave share one in-order vmcnt queue, see the forward)
         pn_acc_zero(acc);
@@ -886,7 +916,8 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
             if (p >= 0) atomicAdd(&a.g_emb[(long long)p * PN_F + col], dx[r * LDX + col]);
         }
         if constexpr (XYZG) b_xyz_row(a, dx + row * LDX, gwf, wrow, wnrm, sidx, rp, row, q, K, kinv, rs.inv(row));
-        PN_TR(pn_trace_bwd, 16);
+        if constexpr (!CLAIM) t_cur += grid;
+        PN_TR(pn_trace_bwd, 16); PN_TR_SPAN(pn_span_bwd, a.cls, 1);
     }
     // flush the register-resident partial sums: a workgroup that had no tile has nothing to add; the others first add up their eight row
     // sets in LDS -- atomics of every workgroup on the same 256 addresses serialise in L2 (2048 per workgroup made the two small sample
@@ -1459,7 +1490,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     if (xg && (!ax.xyz || !ax.sample_loc)) return PNERF_E_INVAL;
     const int ncu = pn_cu_count();
     if (!ncu) return PNERF_E_LAUNCH;
-    const int grid_c = pn_capped_grid((n_valid + PN_CTILE - 1) / PN_CTILE, 3LL * ncu);       // 50.8 KB of LDS: three workgroups per CU
+    const int grid_c = pn_tile_grid((n_valid + PN_CTILE - 1) / PN_CTILE, 3LL * ncu);       // 50.8 KB of LDS: three workgroups per CU
     const size_t lds_c = CB_BYTES, lds_a = xg ? BL_BYTES_X : BL_BYTES;
     const bool wg2 = sv.wg2 != 0;                      // two-plane weight-gradient mode (the forward of this step ran in it: same process-wide setting)
     if (wg2) x0_saved = true;
@@ -1474,7 +1505,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     // the forward left the class partition of the valid samples in the saved area (aggregate.hip: pn_classify)
     a.cls_list = sv.cls_list; a.cls_info = sv.cls_info; a.valid_list = sv.cls_list;
     // the scale of this call's gradients (a power of two derived on the device from max |d decoded| over the valid samples)
-    if (hipMemsetAsync(sv.gscale, 0, 4 * sizeof(unsigned), s) != hipSuccess) return PNERF_E_LAUNCH;
+    if (hipMemsetAsync(sv.gscale, 0, PN_GS_WORDS * sizeof(unsigned), s) != hipSuccess) return PNERF_E_LAUNCH;      // (and the tile claim counters)
     hipLaunchKernelGGL(k_grad_max, dim3(pn_capped_grid((n_valid + 255) / 256, 1024)), dim3(256), 0, s, sv.cls_list, st.counters, n_valid, d_grad_decoded, sv.gscale);
     if (a.zo_gs) hipLaunchKernelGGL(k_zero_one_empty, dim3(1), dim3(1), 0, s, a.conf, st.counters, (long long)st.SR * K, a.zo_gs, a.zo_eps, a.g_conf);
     { PnProfScope prof(PNK_COLOR_BWD, s);
@@ -1484,7 +1515,7 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     { PnProfScope prof(PNK_AGG_BWD, s);
       for (int j = 0; j < ncls; ++j) {
           a.cls = j; a.K = kc[j]; a.TS = pn_tile_samples(kc[j]);
-          const int grid_a = pn_capped_grid((n_valid + a.TS - 1) / a.TS, 2LL * ncu);      // worst-case grid, two workgroups per CU
+          const int grid_a = pn_tile_grid((n_valid + a.TS - 1) / a.TS, 2LL * ncu);      // worst-case grid, two workgroups per CU
           if (xg) { static_cast<BwdArgs &>(ax) = a; hipLaunchKernelGGL(kax, dim3(grid_a), dim3(PN_NTHR), lds_a, s, ax); }
           else hipLaunchKernelGGL(kab, dim3(grid_a), dim3(PN_NTHR), lds_a, s, a);
       } }
@@ -1526,5 +1557,8 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
 #ifdef PN_PHASE_TRACE
 extern "C" int pnerf_debug_trace_bwd(void *host, size_t bytes) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(pn_trace_bwd), bytes < sizeof(pn_trace_bwd) ? bytes : sizeof(pn_trace_bwd)) == hipSuccess ? 0 : -1;
+}
+extern "C" int pnerf_debug_span_bwd(void *host, size_t bytes) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(pn_span_bwd), bytes < sizeof(pn_span_bwd) ? bytes : sizeof(pn_span_bwd)) == hipSuccess ? 0 : -1;
 }
 #endif

@@ -94,7 +94,8 @@ struct PnSaved {
     float *arow;                        // per row: pre-activation of the alpha head
     int4 *rmeta;                        // per row: {sample id or -1, point id or -1, bits(normalised weight), bits(final weight)}
     unsigned *lmask;                    // [row tiles][3 layers h1..h3][8 feature blocks][64 lanes]: LeakyReLU sign bits in the accumulator layout
-    unsigned *gscale;                   // [4]: bits of max |d decoded| over the valid samples (the backward derives its scale from it)
+    unsigned *gscale;                   // [PN_GS_WORDS]: [0] bits of max |d decoded| over the valid samples (the backward derives its scale from it);
+                                        // [PN_GS_CLAIM + class] the backward's tile claim counters
     // per valid sample (padded to colour tiles * 64)
     float *fs, *dfs, *c3;               // fp32 rows: aggregated feature [256] and its gradient, last colour post-activation [128]
     uint4 *xck, *c1k, *c2k;             // k-major [samples / 8][288 | 128 | 128] inputs of the three colour layers ([f | view encoding | 0], c1, c2), one plane
@@ -112,7 +113,24 @@ struct PnSaved {
     long long rows, samples;
 };
 // cls_info words: per class c (< PN_NCLS): number of samples, first position in cls_list, first tile; then totals
-enum : int { PN_NCLS = 3, PN_CI_COUNT = 0, PN_CI_VBASE = 4, PN_CI_TBASE = 8, PN_CI_TILES = 12, PN_CI_CTILES = 13 /* colour tiles of the step */, PN_CI_WORDS = 16 };
+enum : int { PN_NCLS = 3, PN_CI_COUNT = 0, PN_CI_VBASE = 4, PN_CI_TBASE = 8, PN_CI_TILES = 12, PN_CI_CTILES = 13 /* colour tiles of the step */,
+              PN_CI_CLAIM = 16 /* the forward's tile claim counters, one per class */, PN_CI_WORDS = 20 };
+// ---- dynamic tile claim of the two tile kernels.  A launch keeps its grid of resident workgroups and its tile index space; a workgroup's first
+// PN_CLAIM_STATIC_* tiles are blockIdx.x + j * gridDim.x (as many as its loop looks ahead: it starts without waiting for anything), every later
+// one comes from a returning atomicAdd on the launch's counter, issued by one lane a tile ahead of its use and handed to the other waves through
+// one LDS word behind barriers the loop has anyway.  Claims ascend, so the chip still works on one moving window of the saved area; a claim at or
+// beyond the tile count ends the workgroup.  Counters are zero at launch: the forward's (cls_info) by the classification's memset, the backward's
+// (gscale words PN_GS_CLAIM ..) by the memset of its launcher.  With one tile per claim every tile iteration claims once: a launch leaves
+// its counter at the number of tiles it ran, the same number every time (the saved area stays bit-reproducible).
+// (k_agg_backward with xyz_grad and f16 cross terms or two planes keeps the static dealing: backward.hip.)
+#ifndef PN_CLAIM_TILES
+#define PN_CLAIM_TILES 1                       // consecutive tiles per claim.  Only 1 is shipped and tested; 2 and 4 were built for one A/B (no better: profiles/dynamic_tiles.json)
+#endif
+enum : int { PN_CLAIM_STATIC_FWD = 4, PN_CLAIM_STATIC_BWD = 2, PN_GS_CLAIM = 4, PN_GS_WORDS = 8 };
+// tile index of claim sequence number m (0, 1, ...) of a workgroup whose latest claimed value is v
+__device__ __forceinline__ int pn_claim_tile(int nstatic, int grid, int v, int m) { return nstatic * grid + v * PN_CLAIM_TILES + m % PN_CLAIM_TILES; }
+// the grid of the tile and colour kernels: `dflt` resident workgroups (a multiple of the CU count), or pnerf_debug_set_tile_grid's cap
+int pn_tile_grid(long long tiles, long long dflt);
 int pn_class_slots(int K, int kc[3]);
 int pn_classify(const PnSaved &sv, const int32_t *d_valid_list, const int32_t *d_counters, const int32_t *d_pidx, int K, long long n_valid, bool train, bool save_x0, hipStream_t s);
 // the layout of the saved area (aggregate.hip): one walk serves the byte count (null base) and the pointers; s.rows / s.samples are set either way
@@ -167,9 +185,20 @@ __device__ __forceinline__ int pn_row_div(int row, unsigned kinv) { return (int)
     } while (0)
 #define PN_TR_ITER_DECL int titer = -1
 #define PN_TR_ITER_NEXT ++titer
+// the life of a workgroup in the launch of the K-rows class (tools/gpu_finish_trace.py): [0] top of its first tile, [1] end of its last
+// tile (every tile overwrites it), [2] tiles it ran
+#define PN_TR_SPAN_DECL(name) __device__ unsigned long long name[PN_TR_WGS * 4]
+#define PN_TR_SPAN(buf, cls, end)                                                                                   \
+    do {                                                                                                            \
+        if (tid == 0 && (cls) == 0 && blockIdx.x < PN_TR_WGS && ((end) || titer == 0)) {                            \
+            buf[(size_t)blockIdx.x * 4 + (end)] = wall_clock64();                                                   \
+            if (end) buf[(size_t)blockIdx.x * 4 + 2] = (unsigned long long)(titer + 1);                             \
+        }                                                                                                           \
+    } while (0)
 #else
 #define PN_TR(buf, ph)
 #define PN_TR_HWID(buf)
 #define PN_TR_ITER_DECL
 #define PN_TR_ITER_NEXT
+#define PN_TR_SPAN(buf, cls, end)
 #endif

@@ -675,6 +675,16 @@ def set_cross_terms(bits, where=None):
     return old, oldw
 
 
+def set_tile_grid(max_workgroups=0):
+    """Tests: cap the grid of the tile and colour kernels at `max_workgroups` (0: the default, as many workgroups as stay resident); which workgroup
+    runs a tile changes no forward result, and gradients only by the order of their atomic additions (pnerf_debug_set_tile_grid).  Returns the
+    previous cap."""
+    old = L.lib().pnerf_debug_set_tile_grid(int(max_workgroups))
+    if old < 0:
+        raise ValueError("the grid cap must be >= 0")
+    return old
+
+
 def arithmetic():
     """(inference products, weight-gradient planes, cross-term bits, cross-term mask as stored): the process-wide settings of
     set_inference_products / set_wgrad_planes / set_cross_terms, read without writing (pnerf_get_arithmetic)."""
