@@ -168,13 +168,16 @@ def gather_neighbors(points, pidx, camrot, campos):
                 conf=g(points["points_conf"][0]))
 
 
-def aggregate(opt, mlp, nb, loc_p, loc_w, ray_dirs, Rw2c=None, kink=None):
+def aggregate(opt, mlp, nb, loc_p, loc_w, ray_dirs, Rw2c=None, kink=None, taps=None):
     """PointAggregator.forward + viewmlp for the lego configuration.
     nb: dict from gather_neighbors with tensors [1,R,SR,K,*]; loc_* / ray_dirs [1,R,SR,3].
     Returns output [1,R,SR,4], ray_valid [1,R,SR] bool, weight [1,R,SR,K], conf_coefficient [1,R,SR,K].
     kink: optional dict that receives, for the tests' LeakyReLU-kink attribution, the smallest |pre-activation| of every
     neighbor row over the four viewmlp layers (`row_min_pre` [n rows], rows in mask order) and of every valid sample over the
-    three colour layers (`sample_min_pre` [n valid samples])."""
+    three colour layers (`sample_min_pre` [n valid samples]).
+    taps: optional dict that receives, per linear layer k, (input x detached, output y with retain_grad()): after backward() the layer's
+    exact operands are X = x and dY = y.grad, and dY.T @ X is weight.grad (rows: neighbor rows in mask order for block* / alpha_branch,
+    valid samples for color_branch)."""
     mask = nb["mask"]
     B, R, SR, K = mask.shape
     dt = loc_w.dtype
@@ -211,6 +214,9 @@ def aggregate(opt, mlp, nb, loc_p, loc_w, ray_dirs, Rw2c=None, kink=None):
             grp = "row" if k.startswith("block") else "sample"
             m = y.detach().abs().min(dim=-1)[0]
             tracked[grp] = m if grp not in tracked else torch.minimum(tracked[grp], m)
+        if taps is not None:
+            y.retain_grad()
+            taps[k] = (x.detach(), y)
         return y
     feat = act(lin(act(lin(feat, "block1.0")), "block1.2"))
     view = ray_dirs.reshape(-1, 3) @ Rt                                                      # :506
@@ -266,7 +272,7 @@ def ray_march(rdist, ray_valid, feats, bg_color=None):
     return color, rgb, opacity, acc, bw, bg_t
 
 
-def render(opt, points, mlp, inp, impl="oracle", q=None, nthreads=1, Rw2c=None, kink=None):
+def render(opt, points, mlp, inp, impl="oracle", q=None, nthreads=1, Rw2c=None, kink=None, taps=None):
     """NeuralPointsRayMarching.forward (neural_points_volumetric_model.py:252-329) on CPU.
     points: dict xyz [N,3], points_embeding [1,N,F], points_conf [1,N,1], points_dir/color [1,N,3]."""
     if q is None:
@@ -274,7 +280,7 @@ def render(opt, points, mlp, inp, impl="oracle", q=None, nthreads=1, Rw2c=None, 
             q = query(opt, points["xyz"].detach(), inp, impl=impl, nthreads=nthreads)
     camrot, campos = inp["camrotc2w"][0], inp["campos"][0]
     nb = gather_neighbors(points, q["sample_pidx"], camrot, campos)
-    feats, ray_valid, w, conf_c = aggregate(opt, mlp, nb, q["sample_loc"], q["sample_loc_w"], q["sample_ray_dirs"], Rw2c=Rw2c, kink=kink)
+    feats, ray_valid, w, conf_c = aggregate(opt, mlp, nb, q["sample_loc"], q["sample_loc_w"], q["sample_ray_dirs"], Rw2c=Rw2c, kink=kink, taps=taps)
     rd = ray_dist(opt, q["sample_loc"], ray_valid)
     color, _, opacity, acc, bw, bg_t = ray_march(rd, ray_valid, feats, inp["bg_color"])
     return dict(coarse_raycolor=color, coarse_point_opacity=opacity, coarse_is_background=bg_t,
@@ -283,7 +289,7 @@ def render(opt, points, mlp, inp, impl="oracle", q=None, nthreads=1, Rw2c=None, 
                 queried_shading=torch.logical_not(ray_valid.any(dim=-1, keepdim=True)).repeat(1, 1, 3).float())
 
 
-def render_f64(opt, points, mlp, inp, q, Rw2c=None, kink=None):
+def render_f64(opt, points, mlp, inp, q, Rw2c=None, kink=None, taps=None):
     """The same renderer in float64 on the SAME query result q (indices and sample positions stay the fp32 ones): the yardstick
     against which the fp32 oracle's and the HIP path's own rounding (incl. LeakyReLU-kink flips) are measured by the tests."""
     d = lambda t: t.detach().double()
@@ -291,7 +297,7 @@ def render_f64(opt, points, mlp, inp, q, Rw2c=None, kink=None):
     m64 = {k: d(v).requires_grad_(v.requires_grad) for k, v in mlp.items()}
     i64 = {k: (d(v) if isinstance(v, torch.Tensor) and torch.is_floating_point(v) else v) for k, v in inp.items()}
     q64 = {k: (d(v) if isinstance(v, torch.Tensor) and torch.is_floating_point(v) else v) for k, v in q.items()}
-    out = render(opt, pts, m64, i64, q=q64, Rw2c=Rw2c, kink=kink)
+    out = render(opt, pts, m64, i64, q=q64, Rw2c=Rw2c, kink=kink, taps=taps)
     return out, pts, m64
 
 

@@ -24,12 +24,46 @@ extern "C" int pnerf_mlp_layout(int feat_dim, int64_t *offsets) {
     for (int i = 0; i <= PNERF_MLP_NTENSORS; ++i) offsets[i] = o[i];
     return 0;
 }
-extern "C" size_t pnerf_mlp_packed_bytes(void) { return (size_t)PKX_END; }
+extern "C" size_t pnerf_mlp_packed_bytes(void) { return (size_t)PKC_END; }
 
 namespace {
 // two-plane f16 images of the aggregator and colour layers (f16x3.h): forward W[m][k] (trans = 0: m = output unit, k = input column)
 // and dgrad W^T[m][k] (trans = 1: m = input column, k = output unit)
-struct PackHDesc { int src, ld, trans, Mreal, Kreal, NCH, MB, dst; };
+// cm1 / ck1 (dgrad images only; 0 = none): first unit + 1 of the column scales (mixq.h: PN_CS_*) of the image's m / k index -- the image then holds
+// W^T[m][k] c[m] / c[k]; m beyond the layer's units (the extras of layer 3) has no scale
+struct PackHDesc { int src, ld, trans, Mreal, Kreal, NCH, MB, dst, cm1, ck1; };
+__device__ __forceinline__ float pn_pack_scale(const char *packed, int cm1, int ck1, int m, int k) {
+    float f = 1.f;
+    if (cm1 && m < (cm1 - 1 < PN_CS_C1 ? PN_H : PN_HC)) f = pn_col_scale(packed, cm1 - 1)[m];
+    if (ck1) f *= pn_col_scale_inv(packed, ck1 - 1)[k];
+    return f;
+}
+// the column scales of the seven hidden layers (mixq.h): one workgroup per layer, a thread per unit
+struct ColScaleDesc { int first, units, n_cons; struct { int src, ld, rows; } cons[2]; };
+struct ColScaleTable { ColScaleDesc d[7]; };
+__global__ __launch_bounds__(256) void k_pack_colscale(ColScaleTable t, const float *__restrict__ params, char *__restrict__ packed) {
+    __shared__ unsigned red[256];
+    const ColScaleDesc d = t.d[blockIdx.x];
+    const int j = threadIdx.x;
+    float mx = 0.f;
+    if (j < d.units)
+        for (int c = 0; c < d.n_cons; ++c)
+            for (int r = 0; r < d.cons[c].rows; ++r) mx = fmaxf(mx, fabsf(params[d.cons[c].src + r * d.cons[c].ld + j]));
+    const unsigned mb = __float_as_uint(mx);
+    const bool ok = mb >= 0x00800000u && mb < 0x7f800000u;          // (a zero / subnormal / non-finite column takes no scale and sets no reference)
+    red[j] = ok ? mb : 0u;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (j < off) red[j] = red[j] > red[j + off] ? red[j] : red[j + off];
+        __syncthreads();
+    }
+    if (j >= d.units) return;
+    int e = ok ? (int)(red[0] >> 23) - (int)(mb >> 23) : 0;           // binades below the layer's largest column
+    e = e > PN_CS_MAXE ? PN_CS_MAXE : e;
+    float *cs = reinterpret_cast<float *>(packed + PKC_SCALE);
+    cs[d.first + j] = __uint_as_float((unsigned)(127 + e) << 23);
+    cs[PN_CS_UNITS + d.first + j] = __uint_as_float((unsigned)(127 - e) << 23);
+}
 struct PackHTable { PackHDesc d[15]; };
 __global__ __launch_bounds__(256) void k_pack_h(PackHTable t, const float *__restrict__ params, char *__restrict__ packed) {
     const PackHDesc d = t.d[blockIdx.y];
@@ -45,7 +79,7 @@ __global__ __launch_bounds__(256) void k_pack_h(PackHTable t, const float *__res
             for (int i = 0; i < 2; ++i) {
                 const int k = k0 + 2 * j + i;
                 v[i] = 0.f;
-                if (m < d.Mreal && k < d.Kreal) v[i] = d.trans ? params[d.src + k * d.ld + m] : params[d.src + m * d.ld + k];
+                if (m < d.Mreal && k < d.Kreal) v[i] = d.trans ? params[d.src + k * d.ld + m] * pn_pack_scale(packed, d.cm1, d.ck1, m, k) : params[d.src + m * d.ld + k];
             }
             // weights: high plane rounded to NEAREST (v_cvt_pk_f16_f32), residual as always -- h + m is the same 22-bit number for the
             // three-product GEMMs, and h alone is the unbiased best single f16 of the weight, which is what the two-product inference
@@ -61,12 +95,14 @@ __global__ __launch_bounds__(256) void k_pack_h(PackHTable t, const float *__res
 
 // mixed-format images of the eight aggregator GEMMs (mixq.h): per (superchunk, feature block, lane) four f16 h fragments, two e4m3 fragments
 // [q8(wm 2^11 / 2^e) x 8 | q8(wh / 2^e) x 8] per 8-column group with the lane's block scale e, then the classic two-plane tail chunks
-struct PackMDesc { int src, ld, trans, Mreal, Kreal, NT, MB, dst; };
+struct PackMDesc { int src, ld, trans, Mreal, Kreal, NT, MB, dst, cm1, ck1; };
 struct PackMTable { PackMDesc d[9]; };
 __global__ __launch_bounds__(256) void k_pack_mix(PackMTable t, const float *__restrict__ params, char *__restrict__ packed) {
     pn_mode_saturate();
     const PackMDesc d = t.d[blockIdx.y];
-    auto W = [&](int m, int k) -> float { return (m < d.Mreal && k < d.Kreal) ? (d.trans ? params[d.src + k * d.ld + m] : params[d.src + m * d.ld + k]) : 0.f; };
+    auto W = [&](int m, int k) -> float {
+        return (m < d.Mreal && k < d.Kreal) ? (d.trans ? params[d.src + k * d.ld + m] * pn_pack_scale(packed, d.cm1, d.ck1, m, k) : params[d.src + m * d.ld + k]) : 0.f;
+    };
     uint4 *img = reinterpret_cast<uint4 *>(packed + d.dst);
     unsigned *sc = reinterpret_cast<unsigned *>(img + PN_MIMG_U4(d.NT, d.MB));
     const int nsup = PN_MIX_NS * d.MB * 64, ntail = d.NT * d.MB * 64;
@@ -153,32 +189,43 @@ extern "C" int pnerf_mlp_pack(const float *d_params, void *d_packed, void *strea
         {PO_W2, PN_H, 0, PN_H, PN_H, 16, 8, PKH_F2},
         {PO_W3, PN_IN3, 0, PN_H, PN_IN3, 17, 8, PKH_F3},
         {PO_W4, PN_H, 0, PN_H, PN_H, 16, 8, PKH_F4},
-        {PO_W4, PN_H, 1, PN_H, PN_H, 16, 8, PKH_D4},
-        {PO_W3, PN_IN3, 1, PN_IN3, PN_H, 16, 9, PKH_D3},
-        {PO_W2, PN_H, 1, PN_H, PN_H, 16, 8, PKH_D2},
-        {PO_W1, PN_IN1, 1, 32 * PN_MB_D1, PN_H, 16, PN_MB_D1, PKH_D1},
+        {PO_W4, PN_H, 1, PN_H, PN_H, 16, 8, PKH_D4, PN_CS_L3 + 1, PN_CS_L4 + 1},
+        {PO_W3, PN_IN3, 1, PN_IN3, PN_H, 16, 9, PKH_D3, PN_CS_L2 + 1, PN_CS_L3 + 1},
+        {PO_W2, PN_H, 1, PN_H, PN_H, 16, 8, PKH_D2, PN_CS_L1 + 1, PN_CS_L2 + 1},
+        {PO_W1, PN_IN1, 1, 32 * PN_MB_D1, PN_H, 16, PN_MB_D1, PKH_D1, 0, PN_CS_L1 + 1},
         // colour MLP: forward W[m][k], dgrad W^T[m][k] (first 256 input columns of layer 1: the view encoding has no gradient)
         {PO_WC1, PN_INC, 0, PN_HC, PN_INC, 18, 4, PKH_FC1},
         {PO_WC2, PN_HC, 0, PN_HC, PN_HC, 8, 4, PKH_FC2},
         {PO_WC3, PN_HC, 0, PN_HC, PN_HC, 8, 4, PKH_FC3},
-        {PO_WC3, PN_HC, 1, PN_HC, PN_HC, 8, 4, PKH_DC3},
-        {PO_WC2, PN_HC, 1, PN_HC, PN_HC, 8, 4, PKH_DC2},
-        {PO_WC1, PN_INC, 1, PN_H, PN_HC, 8, 8, PKH_DC1},
+        {PO_WC3, PN_HC, 1, PN_HC, PN_HC, 8, 4, PKH_DC3, PN_CS_C2 + 1, PN_CS_C3 + 1},
+        {PO_WC2, PN_HC, 1, PN_HC, PN_HC, 8, 4, PKH_DC2, PN_CS_C1 + 1, PN_CS_C2 + 1},
+        {PO_WC1, PN_INC, 1, PN_H, PN_HC, 8, 8, PKH_DC1, PN_CS_L4 + 1, PN_CS_C1 + 1},          // (d f leaves x the h4 units' scales: b_front)
         // xyz_grad: d X0 columns 224 .. 287 (W1^T rows 224 .. 283, the distance encoding; rows 284 .. 287 zero)
-        {PO_W1 + 32 * PN_MB_D1, PN_IN1, 1, PN_IN1 - 32 * PN_MB_D1, PN_H, 16, 2, PKH_D1T},
+        {PO_W1 + 32 * PN_MB_D1, PN_IN1, 1, PN_IN1 - 32 * PN_MB_D1, PN_H, 16, 2, PKH_D1T, 0, PN_CS_L1 + 1},
+    }};
+    // the hidden units' column scales first (mixq.h): from the columns of every consumer's weight; the dgrad images below are built with them
+    const ColScaleTable tc = {{
+        {PN_CS_L1, PN_H, 1, {{PO_W2, PN_H, PN_H}}},
+        {PN_CS_L2, PN_H, 1, {{PO_W3, PN_IN3, PN_H}}},
+        {PN_CS_L3, PN_H, 1, {{PO_W4, PN_H, PN_H}}},
+        {PN_CS_L4, PN_H, 2, {{PO_W5, PN_H, 1}, {PO_WC1, PN_INC, PN_HC}}},
+        {PN_CS_C1, PN_HC, 1, {{PO_WC2, PN_HC, PN_HC}}},
+        {PN_CS_C2, PN_HC, 1, {{PO_WC3, PN_HC, PN_HC}}},
+        {PN_CS_C3, PN_HC, 1, {{PO_WC4, PN_HC, 3}}},
     }};
     PnProfScope prof(PNK_PACK, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_pack_colscale, dim3(7), dim3(256), 0, (hipStream_t)stream, tc, d_params, (char *)d_packed);
     hipLaunchKernelGGL(k_pack_h, dim3(40, 15), dim3(256), 0, (hipStream_t)stream, th, d_params, (char *)d_packed);
     PackMTable tm = {{
         {PO_W1, PN_IN1, 0, PN_H, PN_IN1, 2, 8, PKM_F1},
         {PO_W2, PN_H, 0, PN_H, PN_H, 0, 8, PKM_F2},
         {PO_W3, PN_IN3, 0, PN_H, PN_IN3, 1, 8, PKM_F3},
         {PO_W4, PN_H, 0, PN_H, PN_H, 0, 8, PKM_F4},
-        {PO_W4, PN_H, 1, PN_H, PN_H, 0, 8, PKM_D4},
-        {PO_W3, PN_IN3, 1, PN_IN3, PN_H, 0, 9, PKM_D3},
-        {PO_W2, PN_H, 1, PN_H, PN_H, 0, 8, PKM_D2},
-        {PO_W1, PN_IN1, 1, 32 * PN_MB_D1, PN_H, 0, PN_MB_D1, PKM_D1},
-        {PO_W1 + 32 * PN_MB_D1, PN_IN1, 1, PN_IN1 - 32 * PN_MB_D1, PN_H, 0, 2, PKM_D1T},
+        {PO_W4, PN_H, 1, PN_H, PN_H, 0, 8, PKM_D4, PN_CS_L3 + 1, PN_CS_L4 + 1},
+        {PO_W3, PN_IN3, 1, PN_IN3, PN_H, 0, 9, PKM_D3, PN_CS_L2 + 1, PN_CS_L3 + 1},
+        {PO_W2, PN_H, 1, PN_H, PN_H, 0, 8, PKM_D2, PN_CS_L1 + 1, PN_CS_L2 + 1},
+        {PO_W1, PN_IN1, 1, 32 * PN_MB_D1, PN_H, 0, PN_MB_D1, PKM_D1, 0, PN_CS_L1 + 1},
+        {PO_W1 + 32 * PN_MB_D1, PN_IN1, 1, PN_IN1 - 32 * PN_MB_D1, PN_H, 0, 2, PKM_D1T, 0, PN_CS_L1 + 1},
     }};
     hipLaunchKernelGGL(k_pack_mix, dim3(12, 9), dim3(256), 0, (hipStream_t)stream, tm, d_params, (char *)d_packed);
     PN_CHECK_LAUNCH();

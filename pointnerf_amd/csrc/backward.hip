@@ -3,6 +3,8 @@
 // (f16x3.h); inside the aggregator backward every gradient row carries a power-of-two scale so that it sits in the f16 range, and leaves
 // it multiplied by the exact inverse: the rows of the input-gradient chain the scale S_i of their own SAMPLE (pn_sample_scale; atomics into the
 // point gradients x 1 / S_i), the k-major dY planes of the weight-gradient GEMMs -- sums over rows -- the CALL's scale S (k_grad_max; reduction x 1 / S).
+// Every COLUMN of a dY tile carries the power-of-two scale c_j of its hidden unit as well (mixq.h: derived from the consumers' weights when the
+// images are packed), so that a unit with small outgoing weights keeps its bits in those planes; the reduction multiplies row j by 1 / c_j.
 //
 // The reference gets all of this from torch.autograd over ~60 ATen ops (loss.backward() in
 // models/mvs_points_volumetric_model.py:98-118): cuBLAS dgrad/wgrad per nn.Linear, dense
@@ -141,7 +143,7 @@ __device__ __forceinline__ void pn_copy_out_kmajor_hs(const char *X, const PnRow
 // dgrad chain d c3 x Wc3 -> d c2 x Wc2 -> d c1 x Wc1[:, :256] -> d f as two-plane f16 GEMMs on gradient rows that carry the power-of-two
 // scale S_i of their own sample (pn_sample_scale).  The LeakyReLU masks are the forward's sign words (c1, c2) and the saved fp32 c3; d c1..d c3 leave
 // k-major as one f16 plane at the CALL's scale S (rows x S / S_i) for the weight-gradient GEMMs of these layers, d f as fp32 rows (x 1 / S_i) for
-// k_agg_backward.
+// k_agg_backward.  Every d c column, and every d f column, carries its unit's column scale (mixq.h: the images hold them; d c3 gets it from w4s).
 // LDS: the tile, d raw [64][4] (slot 3: S_i), the rows' scale records, and the running sums of d Wc4 [3][128], d bc3, d bc2, d bc1 [128], one set per wave (plain LDS
 // adds by the address's one owner lane; kept in registers they are 45 loop-carried values per thread next to the GEMM's working set)
 // The tile holds 128 columns at most (d c3, d c2, d c1): its rows are 272 bytes apart (68 dwords = 4 mod 64 banks: the GEMM's 16-byte fragment
@@ -228,7 +230,8 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
     long long si_cur = row_sample(blockIdx.x);
     row_values(si_cur);
     float *w4s = reinterpret_cast<float *>(smem_cb + CB_W4);             // Wc4 [3][128] (the colour tensors sit at odd float offsets in the flat vector)
-    for (int i = threadIdx.x; i < 3 * PN_HC; i += 256) w4s[i] = P[PO_WC4 + i];
+    // x the column scale of the c3 unit (mixq.h): d c3 -- and with it d bc3's running sum -- is formed scaled; the dgrad images carry the scales on
+    for (int i = threadIdx.x; i < 3 * PN_HC; i += 256) w4s[i] = P[PO_WC4 + i] * pn_col_scale(a.packed, PN_CS_C3)[i & (PN_HC - 1)];
 
     f32x16 acc[2][2];
     for (long long tile = blockIdx.x; tile * PN_CTILE < Ns; tile += gridDim.x) {
@@ -346,9 +349,10 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
         auto total = [&](int i) { return (gacc[i] + gacc[CB_GSUMS + i]) + (gacc[2 * CB_GSUMS + i] + gacc[3 * CB_GSUMS + i]); };      // the four waves' sets
         for (int i = tid; i < 3 * PN_HC; i += 256) atomicAdd(&a.gparams[PO_WC4 + i], total(i));
         if (tid < PN_HC) {
-            atomicAdd(&a.gparams[PO_BC3 + tid], total(3 * PN_HC + tid));
-            atomicAdd(&a.gparams[PO_BC2 + tid], total(4 * PN_HC + tid) * invS);
-            atomicAdd(&a.gparams[PO_BC1 + tid], total(5 * PN_HC + tid) * invS);
+            // (column sums of scaled d c tiles: x 1 / the unit's column scale)
+            atomicAdd(&a.gparams[PO_BC3 + tid], total(3 * PN_HC + tid) * pn_col_scale_inv(a.packed, PN_CS_C3)[tid]);
+            atomicAdd(&a.gparams[PO_BC2 + tid], total(4 * PN_HC + tid) * invS * pn_col_scale_inv(a.packed, PN_CS_C2)[tid]);
+            atomicAdd(&a.gparams[PO_BC1 + tid], total(5 * PN_HC + tid) * invS * pn_col_scale_inv(a.packed, PN_CS_C1)[tid]);
         }
         if (tid < PN_CTILE) {                              // d bc4: the row threads' partial column sums (wave 0)
 #pragma unroll
@@ -366,7 +370,8 @@ __global__ __launch_bounds__(256, 3) void k_color_backward(BwdArgs a) {
 //   -> layer-3 extras (d colour, d dir) as a ninth feature block, K split over the four waves
 //   -> d X0 (224 columns: the embedding and its encoding) as fp32 in LDS -> PE chain rule -> atomics into the touched points.
 // Bias gradients are not formed here: they are the ones-column of the weight-gradient GEMMs.
-constexpr int BL_ROW = PN_XBYTES, BL_RSC = BL_ROW + 10 * PN_TILE * 4, BL_W5 = BL_RSC + PN_RSC_BYTES, BL_CLAIM = BL_W5 + PN_H * 4 /* the claimed tile: one word */, BL_BYTES = BL_CLAIM + 16;
+constexpr int BL_ROW = PN_XBYTES, BL_RSC = BL_ROW + 10 * PN_TILE * 4, BL_W5 = BL_RSC + PN_RSC_BYTES, BL_CLAIM = BL_W5 + PN_H * 4 /* the claimed tile: one word */,
+              BL_C4 = BL_CLAIM + 16 /* 1 / the column scales of the h4 units (mixq.h); the alpha head's weights w5s are held x those scales */, BL_BYTES = BL_C4 + PN_H * 4;
 constexpr int LDDX = 228;                      // fp32 row stride of the d X0 tile (over the activation tile's space)
 static_assert(2 * BL_BYTES <= 160 * 1024, "two backward workgroups must fit the 160 KB LDS");
 static_assert(PN_TILE * LDDX * 4 <= PN_XBYTES, "d X0 tile");
@@ -419,7 +424,7 @@ __device__ __forceinline__ void b_epilogue(const f32x16 (&acc)[PN_NFB][2], const
 // group's e4m3 unit [q8(h) x 8 | q8(m 2^11) x 8] -- a thread still rewrites only bytes it alone reads
 // XG (xyz_grad): the row's d w (d sigma alpha + d f . h4, x S_i; 0 for a row without a point) also goes to gwf[row] for the weight chain
 template <int KC, bool MIX = false, bool XG = false>
-__device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *w5s, const float *wrow, const float *wnrm, const float *dsg, const float *xrow,
+__device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *w5s, const float *c4is, const float *wrow, const float *wnrm, const float *dsg, const float *xrow,
                                         float *draw, const int *sidx, const int *prow, const float4 (&dfr)[4], const float *dfb0, const PnRowScale &rs, int tid,
                                         float (&gw5)[8], float &gb5t, unsigned kinv = 0u, float *gwf = nullptr) {
     const int lane = tid & 63, cg = tid & 31, r0 = 8 * (tid >> 5);
@@ -436,6 +441,9 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
         if (KC >= 4) { ga = dfr[2 * j]; gb = dfr[2 * j + 1]; }
         else { ga = *reinterpret_cast<const float4 *>(dfb0 + j * PN_H); gb = *reinterpret_cast<const float4 *>(dfb0 + j * PN_H + 4); }
     };
+    // The d f rows arrive x the column scales c of the h4 units (mixq.h: k_color_backward's last image carries them), which is how dY4 leaves
+    // -- w5s holds W5 x c as well --; the dot product d f . h4 takes them x 1 / c (c4is)
+    const float4 cia = *reinterpret_cast<const float4 *>(c4is + 8 * cg), cib = *reinterpret_cast<const float4 *>(c4is + 8 * cg + 4);
     float pd[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -444,6 +452,7 @@ __device__ __forceinline__ void b_front(const BwdArgs &a, char *X, const float *
         const uint4 m = *reinterpret_cast<const uint4 *>(X + PN_XPLANE + r * PN_XRS + cg * 16);
         float4 ga, gb;
         df_of(j, ga, gb);
+        ga.x *= cia.x; ga.y *= cia.y; ga.z *= cia.z; ga.w *= cia.w; gb.x *= cib.x; gb.y *= cib.y; gb.z *= cib.z; gb.w *= cib.w;
         float s = 0.f;
         s = pn_fma2_lo(h.x, m.x, ga.x, s); s = pn_fma2_hi(h.x, m.x, ga.y, s); s = pn_fma2_lo(h.y, m.y, ga.z, s); s = pn_fma2_hi(h.y, m.y, ga.w, s);
         s = pn_fma2_lo(h.z, m.z, gb.x, s); s = pn_fma2_hi(h.z, m.z, gb.y, s); s = pn_fma2_lo(h.w, m.w, gb.z, s); s = pn_fma2_hi(h.w, m.w, gb.w, s);
@@ -587,7 +596,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
     const PnRowScale rs{reinterpret_cast<float *>(smem_b + BL_RSC)};
     int *sidx = reinterpret_cast<int *>(xrow + PN_TILE), *prow = sidx + PN_TILE;
     float *rdir = reinterpret_cast<float *>(prow + PN_TILE);          // [3][64] the rows' ray directions (for d dir, behind layer 3)
-    float *w5s = reinterpret_cast<float *>(smem_b + BL_W5);
+    float *w5s = reinterpret_cast<float *>(smem_b + BL_W5), *c4is = reinterpret_cast<float *>(smem_b + BL_C4);
     float *dx = reinterpret_cast<float *>(smem_b);
     float *gwf = XYZG ? reinterpret_cast<float *>(smem_b + BL_GW) : nullptr;
     const int tid0 = threadIdx.x;
@@ -601,7 +610,7 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
     const char *img = reinterpret_cast<const char *>(a.packed);
     float S, invS;
     pn_scale_from_bits(a.sv.gscale[0], S, invS);
-    if (tid0 < PN_H) w5s[tid0] = P[PO_W5 + tid0];
+    if (tid0 < PN_H) { w5s[tid0] = P[PO_W5 + tid0] * pn_col_scale(a.packed, PN_CS_L4)[tid0]; c4is[tid0] = pn_col_scale_inv(a.packed, PN_CS_L4)[tid0]; }
     float gw5[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // d W5 of columns 8 (tid & 31) .. + 7 (x S)
     float gb5t = 0.f;
     f32x16 acc[PN_NFB][2];
@@ -712,11 +721,11 @@ __global__ __launch_bounds__(PN_NTHR, PN_NW / 2) void k_agg_backward(typename Bw
         }
         {
             // ---- alpha head backward + dY4 in one pass (b_front): K = 8 / 4 / 2 / 1 with compile-time sample boundaries, any other K at run time
-            if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
-            else if (K == 4) b_front<4, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
-            else if (K == 2) b_front<2, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
-            else if (K == 1) b_front<1, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
-            else b_front<0, MIX, XYZG>(a, X, w5s, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, kinv, gwf);
+            if (K == 8) b_front<8, MIX, XYZG>(a, X, w5s, c4is, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 4) b_front<4, MIX, XYZG>(a, X, w5s, c4is, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 2) b_front<2, MIX, XYZG>(a, X, w5s, c4is, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else if (K == 1) b_front<1, MIX, XYZG>(a, X, w5s, c4is, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, 0u, gwf);
+            else b_front<0, MIX, XYZG>(a, X, w5s, c4is, wrow, wnrm, dsg, xrow, draw, sidx, prow, dfr, dfb0, rs, tid, gw5, gb5t, kinv, gwf);
             PN_TR(pn_trace_bwd, 2);
         }
         // (round 4: the first weight-fragment chunks of every GEMM are requested in FRONT of the barrier that precedes it -- see the forward)
@@ -1136,9 +1145,10 @@ __global__ __launch_bounds__(512) void k_wgrad_f16(const uint4 *__restrict__ A, 
     }
 }
 
-// grad_w[m * ldc + n] += invS * sum_c partial[c][m][n]  (m < Mreal, n < Nreal);  grad_b[m] += invS * sum_c partial[c][m][bias_col]
+// grad_w[m * ldc + n] += invS / c_m * sum_c partial[c][m][n]  (m < Mreal, n < Nreal);  grad_b[m] += invS / c_m * sum_c partial[c][m][bias_col]
+// cinv[m] = 1 / c_m: the dY planes carry unit m's column x its column scale (mixq.h), a power of two, undone here exactly
 __global__ __launch_bounds__(256) void k_wgrad_reduce_f16(const float *__restrict__ partial, int chunks, int Mreal, int Nreal, int bias_col, const unsigned *__restrict__ gscale,
-                                                          float *__restrict__ grad, int dst_w, int ldc, int dst_b) {
+                                                          const float *__restrict__ cinv, float *__restrict__ grad, int dst_w, int ldc, int dst_b) {
     __shared__ float part[4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int e = blockIdx.x * 64 + lane;
@@ -1154,7 +1164,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_f16(const float *__restric
         float S, invS;
         pn_scale_from_bits(gscale[0], S, invS);
         const int m = e / 288, n = e - m * 288;
-        const float v = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) * invS;
+        const float v = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) * invS * cinv[m];
         if (n < Nreal) grad[dst_w + m * ldc + n] += v;
         else if (n == bias_col) grad[dst_b + m] += v;
     }
@@ -1168,6 +1178,7 @@ struct WgLayer {
     const int *d_tiles;                 // the device's count of 64-row tiles to walk
     long long rows_max;                 // its host bound: the allocation
     int dst_w, ldc, nreal, bias_col, dst_b;
+    const float *cinv;                  // 1 / column scale of the layer's units (the rows of dW)
 };
 template <int NFB, int MF, int RS, int NST, bool TWO>
 int launch_wgrad_f16(const WgLayer &L, float *partial, const unsigned *gscale, float *grad, hipStream_t s) {
@@ -1183,7 +1194,7 @@ int launch_wgrad_f16(const WgLayer &L, float *partial, const unsigned *gscale, f
     { PnProfScope prof(PNK_WGRAD, s);
     hipLaunchKernelGGL((k_wgrad_f16<NFB, MF, RS, NST, TWO>), dim3(chunks), dim3(512), lds, s, L.dy, L.x, L.d_tiles, partial, L.dym, L.xm); }
     PnProfScope prof(PNK_WGRAD_REDUCE, s);
-    hipLaunchKernelGGL(k_wgrad_reduce_f16, dim3(pn_cdiv((long long)MF * 288, 64)), dim3(256), 0, s, partial, chunks, MF, L.nreal, L.bias_col, gscale, grad, L.dst_w, L.ldc, L.dst_b);
+    hipLaunchKernelGGL(k_wgrad_reduce_f16, dim3(pn_cdiv((long long)MF * 288, 64)), dim3(256), 0, s, partial, chunks, MF, L.nreal, L.bias_col, gscale, L.cinv, grad, L.dst_w, L.ldc, L.dst_b);
     PN_CHECK_LAUNCH();
     return 0;
 }
@@ -1435,7 +1446,7 @@ __global__ __launch_bounds__(512) void k_wgrad_x0(const uint4 *__restrict__ A, W
     }
 }
 
-int launch_wgrad_x0(const uint4 *A, const WgX0Args &g, const int *d_tiles, long long rows_max, float *partial, const unsigned *gscale,
+int launch_wgrad_x0(const uint4 *A, const WgX0Args &g, const int *d_tiles, long long rows_max, float *partial, const unsigned *gscale, const float *cinv,
                     float *grad, hipStream_t s) {
     int chunks = WG_CHUNKS;
     const long long tiles = rows_max / PN_TILE;
@@ -1446,7 +1457,7 @@ int launch_wgrad_x0(const uint4 *A, const WgX0Args &g, const int *d_tiles, long 
     { PnProfScope prof(PNK_WGRAD, s);
     hipLaunchKernelGGL(k_wgrad_x0, dim3(chunks), dim3(512), lds, s, A, g, d_tiles, partial); }
     PnProfScope prof(PNK_WGRAD_REDUCE, s);
-    hipLaunchKernelGGL(k_wgrad_reduce_f16, dim3(pn_cdiv((long long)PN_H * 288, 64)), dim3(256), 0, s, partial, chunks, PN_H, PN_IN1, PN_ONES1, gscale, grad, (int)PO_W1, (int)PN_IN1, (int)PO_B1);
+    hipLaunchKernelGGL(k_wgrad_reduce_f16, dim3(pn_cdiv((long long)PN_H * 288, 64)), dim3(256), 0, s, partial, chunks, PN_H, PN_IN1, PN_ONES1, gscale, cinv, grad, (int)PO_W1, (int)PN_IN1, (int)PO_B1);
     PN_CHECK_LAUNCH();
     return 0;
 }
@@ -1531,21 +1542,23 @@ int pn_agg_backward_launch(const pnerf_camera *cam, const pnerf_points *pts, con
     // the four aggregator layers (the bias gradients are the operands' own ones column in layers 1 and 3, the constant-ones tail in layers 2 and
     // 4; in two-plane mode they take both planes of dY: the ones column has a zero residual, the tail is multiplied with dYh and dYm), then the
     // three colour layers: samples instead of neighbor rows, 128 output features; their bias gradients were summed by k_color_backward
+    // (every dY plane carries its units' column scales, mixq.h: the reductions undo them per row of dW)
+    const float *ci = reinterpret_cast<const float *>(reinterpret_cast<const char *>(st.packed_mlp) + PKC_SCALE) + PN_CS_UNITS;
     const WgLayer layers[7] = {
-        {WG_288x256, sv.dy1k, sv.x0k, sv.dy1m, sv.x0m, dt, rows, PO_W1, PN_IN1, PN_IN1, PN_ONES1, PO_B1},
-        {WG_256x256, sv.dy2k, sv.h1k, sv.dy2m, sv.h1m, dt, rows, PO_W2, PN_H, PN_H, PN_H, PO_B2},
-        {WG_288x256, sv.dy3k, sv.h2k, sv.dy3m, sv.h2m, dt, rows, PO_W3, PN_IN3, PN_IN3, PN_ONES3, PO_B3},
-        {WG_256x256, sv.dy4k, sv.h3k, sv.dy4m, sv.h3m, dt, rows, PO_W4, PN_H, PN_H, PN_H, PO_B4},
-        {WG_288x128, sv.dc1k, sv.xck, sv.dc1m, sv.xcm, ct, smps, PO_WC1, PN_INC, PN_INC, -1, 0},
-        {WG_128x128, sv.dc2k, sv.c1k, sv.dc2m, sv.c1m, ct, smps, PO_WC2, PN_HC, PN_HC, -1, 0},
-        {WG_128x128, sv.dc3k, sv.c2k, sv.dc3m, sv.c2m, ct, smps, PO_WC3, PN_HC, PN_HC, -1, 0},
+        {WG_288x256, sv.dy1k, sv.x0k, sv.dy1m, sv.x0m, dt, rows, PO_W1, PN_IN1, PN_IN1, PN_ONES1, PO_B1, ci + PN_CS_L1},
+        {WG_256x256, sv.dy2k, sv.h1k, sv.dy2m, sv.h1m, dt, rows, PO_W2, PN_H, PN_H, PN_H, PO_B2, ci + PN_CS_L2},
+        {WG_288x256, sv.dy3k, sv.h2k, sv.dy3m, sv.h2m, dt, rows, PO_W3, PN_IN3, PN_IN3, PN_ONES3, PO_B3, ci + PN_CS_L3},
+        {WG_256x256, sv.dy4k, sv.h3k, sv.dy4m, sv.h3m, dt, rows, PO_W4, PN_H, PN_H, PN_H, PO_B4, ci + PN_CS_L4},
+        {WG_288x128, sv.dc1k, sv.xck, sv.dc1m, sv.xcm, ct, smps, PO_WC1, PN_INC, PN_INC, -1, 0, ci + PN_CS_C1},
+        {WG_128x128, sv.dc2k, sv.c1k, sv.dc2m, sv.c1m, ct, smps, PO_WC2, PN_HC, PN_HC, -1, 0, ci + PN_CS_C2},
+        {WG_128x128, sv.dc3k, sv.c2k, sv.dc3m, sv.c2m, ct, smps, PO_WC3, PN_HC, PN_HC, -1, 0, ci + PN_CS_C3},
     };
     for (const WgLayer &L : layers) {
         int rc;
         if (&L == layers && !x0_saved) {       // layer 1 on the fused path: X0 rebuilt from the gather (the stand-alone aggregator's forward saved its planes)
             WgX0Args wa;
             wa.rmeta = sv.rmeta; wa.emb = pts->embedding; wa.x0t = sv.x0k; wa.n_points = pts->n;
-            rc = launch_wgrad_x0(L.dy, wa, dt, rows, d_partials, sv.gscale, d_grad_params, s);
+            rc = launch_wgrad_x0(L.dy, wa, dt, rows, d_partials, sv.gscale, L.cinv, d_grad_params, s);
         } else {
             rc = wg2 ? launch_wgrad_layer<true>(L, d_partials, sv.gscale, d_grad_params, s) : launch_wgrad_layer<false>(L, d_partials, sv.gscale, d_grad_params, s);
         }

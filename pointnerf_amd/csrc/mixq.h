@@ -55,6 +55,22 @@ enum : int {
 // xyz_grad (k_agg_backward<.., XYZG>): the two feature blocks of d X0 behind the seven above, columns 224 .. 287 (the distance encoding), as
 // W1^T rows 224 .. 287 in either arithmetic.  Placed behind every other image so that no offset the other kernels use moves.
 enum : int { PKH_D1T = PKM_END, PKM_D1T = PKH_D1T + PN_IMG(16, 2), PKX_END = PKM_D1T + PN_MIMG(0, 2) };
+// The hidden units' column scales (k_pack_colscale, aggregate.hip), behind every image: float [2][PN_CS_UNITS] = c | 1 / c, units in the order
+// of the PN_CS_* offsets.  c_j = the power of two that brings the largest |weight| among the CONSUMERS' columns j up to the binade of the layer's
+// largest such column (1 <= c_j <= 2^PN_CS_MAXE).  A unit whose outgoing weights are small has a uniformly small dY column, which in the f16 planes
+// of the gradient tiles falls into the subnormals or flushes: its row of dW and its bias gradient were noise.  The backward therefore carries
+// dY'[:, j] = c_j dY[:, j]: the dgrad images hold W'[i][j] = W[j][i] c_in[i] / c_out[j] (exact powers of two; the colour MLP's last image also
+// carries the h4 units' scales, so that d f arrives scaled), the two places that form a dY tile on the VALU take their weights x c (d c3: Wc4; dY4:
+// W5, next to the scaled d f), and whoever sums a dY' column over rows (weight-gradient reduction, bias sums) multiplies by 1 / c_j.  A row of
+// W' that a large c_out[j] pushes into the f16 subnormals keeps an absolute error of 2^-25 per weight: what an ordinary weight's 22 bits leave.
+// Where all columns of a layer's consumers peak in the same binade every c is 1 and nothing changes, bit for bit; a power of two commutes with
+// every rounding of the chain except at the subnormal end, so elsewhere the gradients move by the e4m3 cross terms' block exponents only.
+enum : int { PN_CS_L1 = 0, PN_CS_L2 = PN_H, PN_CS_L3 = 2 * PN_H, PN_CS_L4 = 3 * PN_H, PN_CS_C1 = 4 * PN_H, PN_CS_C2 = PN_CS_C1 + PN_HC, PN_CS_C3 = PN_CS_C2 + PN_HC,
+              PN_CS_UNITS = PN_CS_C3 + PN_HC, PN_CS_MAXE = 14 };
+enum : int { PKC_SCALE = PKX_END, PKC_END = PKC_SCALE + 2 * PN_CS_UNITS * 4 };
+static_assert(PKC_SCALE % 16 == 0, "the column scales are read as float4");
+__device__ __forceinline__ const float *pn_col_scale(const void *packed, int first_unit) { return reinterpret_cast<const float *>(reinterpret_cast<const char *>(packed) + PKC_SCALE) + first_unit; }
+__device__ __forceinline__ const float *pn_col_scale_inv(const void *packed, int first_unit) { return pn_col_scale(packed, first_unit) + PN_CS_UNITS; }
 
 // MODE.FP16_OVFL = 1: f16 and fp8 conversions saturate instead of producing inf / NaN (per wave; every wave of a tile kernel runs this first)
 __device__ __forceinline__ void pn_mode_saturate() {

@@ -29,8 +29,8 @@ CASES = {
 }
 
 
-def build(name):
-    K, SR, P, size, n, seed, theta, mlp_seed = CASES[name]
+def build(name, cases=CASES):
+    K, SR, P, size, n, seed, theta, mlp_seed = cases[name]
     opt = config.lego_opt(K=K, SR=SR, P=P, max_o=50000, ranges=[-0.3, -0.3, -0.3, 0.3, 0.3, 0.3])
     xyz = torch.from_numpy(scenes.chair_points(n, seed=seed, radius=0.06))
     attrs = {k: torch.from_numpy(v) for k, v in scenes.point_attributes(n, 32, seed).items()}

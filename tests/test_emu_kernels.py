@@ -154,7 +154,7 @@ def test_emulated_backward_by_ray_chunks(monkeypatch):
     (3, 2500, 3, 12, 5, dict(P=40)),                                                 # P beyond the tile rows: the thread-per-sample kernel
 ])
 def test_emulated_neighbor_query_bit_exact(monkeypatch, seed, n, K, SR, size, kw):
-    """k_probe + k_neighbors_tiles (LDS-staged candidate tiles) / k_neighbors: indices, sample positions and masks equal the oracle's"""
+    """k_probe + k_neighbors (one thread per selected sample): indices, sample positions and masks equal the oracle's"""
     import test_gpu_query as TQ
     monkeypatch.setattr(TQ, "DEV", "cpu")
     opt, xyz, inp = TQ._scene(seed, n, K=K, SR=SR, size=size, **kw)
