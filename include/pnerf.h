@@ -483,6 +483,36 @@ int pnerf_geometry_canvas(const int32_t *d_pixel_idx, const int8_t *d_ray_mask, 
                           const float *d_acc, int n_rays, int H, int W, float *d_depth_canvas, float *d_median_canvas, float *d_acc_canvas,
                           int32_t *d_flag, void *stream);
 
+/* ---- point attribute maps, picking and image-to-point lifting of a render-only pass, on the renderer's dense results (no reference
+ * counterpart).  One linear operator A and its adjoint on d_blend_w [R,SR], d_weight [R,SR,K], d_sample_pidx [R,SR,K], d_ray_hit [R] as
+ * pnerf_query / pnerf_render_forward (or _cut) left them.  For ray r, slot s < SR, neighbor slot k < K:
+ *   p = d_sample_pidx[r,s,k];   g[r,s,k] = d_blend_w[r,s] * d_weight[r,s,k] (one fp32 multiply) if 0 <= p < n_points, else 0.
+ * An index outside [0, n_points) -- the empty slot -1 included, which here does NOT read point 0 -- contributes nothing and is never
+ * dereferenced; the weight and index rows of a sample with d_blend_w == 0 are not read.  d_weight is the normalised distance weight (it sums
+ * to 1 over the occupied slots of a valid sample: sum_k g = d_blend_w); the confidence factor of the density is NOT part of g.  A ray with
+ * d_ray_hit[r] <= 0 produces zeros / -1 (pnerf_ray_attributes) or adds nothing (pnerf_lift_to_points); none of its rows are read.
+ *
+ * pnerf_ray_attributes (A and the pick), d_attr [n_points,C] f32:
+ *   d_attr_sum [R,C] = sum_{s,k} g[r,s,k] d_attr[p,c], fp32, in an order that depends on (SR, K, C) only;
+ *   d_top_flat [R] i32 = the LOWEST flat index s*K + k among the maxima of g[r,:,:] -- the largest single (sample, slot) entry, not a
+ *   per-point sum over the ray's samples --, d_top_point [R] i32 = d_sample_pidx there, d_top_contrib [R] = g there; a hit ray whose
+ *   largest g is not > 0 gets -1, -1, 0.  No atomics: two calls give the same bits.  C == 0 runs the pick only.
+ * pnerf_lift_to_points (A^T), d_values [R,C] f32, d_ray_factor [R] f32 (NULL: 1):
+ *   d_point_sum [n_points,C] += g[r,s,k] m[r] d_values[r,c],   d_point_mass [n_points] += g[r,s,k] m[r]   over every entry that addresses p.
+ *   The call ADDS into the caller's accumulators (several views add up; the caller zeroes them) with fp32 atomicAdd on global memory, the
+ *   kind of the backward's point gradients: the sums depend on the order of arrival and are NOT bit-reproducible.
+ * PNERF_E_INVAL: K outside 1..PNERF_MAX_K, SR <= 0, R < 0, n_points <= 0, C < 0, a null pointer (while R > 0; d_ray_factor may be null);
+ * PNERF_E_UNSUP: C > 256 (attributes), C > 8 (lifting).  R == 0: nothing is enqueued.  No allocation, no host read. */
+int pnerf_ray_attributes(const float *d_attr, int32_t n_points, int C,
+        const float *d_blend_w, const float *d_weight, const int32_t *d_sample_pidx, const int32_t *d_ray_hit,
+        int R, int SR, int K,
+        float *d_attr_sum /*[R,C]; may be NULL iff C == 0*/, int32_t *d_top_point, int32_t *d_top_flat, float *d_top_contrib /*[R] each*/,
+        void *stream);
+int pnerf_lift_to_points(const float *d_values /*[R,C] or NULL iff C == 0*/, int C, const float *d_ray_factor /*[R] or NULL*/,
+        const float *d_blend_w, const float *d_weight, const int32_t *d_sample_pidx, const int32_t *d_ray_hit,
+        int R, int SR, int K, int32_t n_points,
+        float *d_point_sum /*[n_points,C] or NULL iff C == 0*/, float *d_point_mass /*[n_points]*/, void *stream);
+
 /* ---- diagnostics: ONE v_mfma_f32_32x32x16_f16, D = A B with caller-built fragments: d_a / d_b [64 lanes][8] f16 (lane l holds
  * A[l & 31][8 (l >> 5) .. + 7] resp. B[8 (l >> 5) .. + 7][l & 31]), d_out [64 lanes][16] f32 (register r of lane l =
  * D[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31]).  The tests pin with it the fragment layout and the un-flushed handling of f16

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1004                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1005                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
@@ -141,6 +141,12 @@ PROTOTYPES = {
     # (pixel_idx, ray_mask, depth, median_depth, acc, n_rays, H, W, depth_canvas, median_canvas, acc_canvas, flag, stream)
     "pnerf_geometry_canvas": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (attr, n_points, C, blend_w, weight, sample_pidx, ray_hit, R, SR, K, attr_sum, top_point, top_flat, top_contrib, stream)
+    "pnerf_ray_attributes": (c_int, [c_void_p, ctypes.c_int32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (values, C, ray_factor, blend_w, weight, sample_pidx, ray_hit, R, SR, K, n_points, point_sum, point_mass, stream)
+    "pnerf_lift_to_points": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_int32,
+                                     c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mfma_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mix_gemm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pnerf_debug_mfma_rate": (c_int, [c_int, c_int, c_void_p, ctypes.POINTER(ctypes.c_double), c_void_p]),

@@ -847,6 +847,89 @@ def check_canvas_flag(flag):
     L.check(int(flag.cpu()[0]), "pnerf_geometry_canvas (a pixel_idx outside the canvas)")
 
 
+# ------------------------------------------------------------------------------------------ point attribute maps, picking, lifting
+RAY_ATTRIBUTES_CMAX, LIFT_CMAX = 256, 8
+
+
+def _ray_entries(blend_w, weight, sample_pidx, ray_hit):
+    """the four dense tensors both point-map ops read, checked by name -> (R, SR, K)"""
+    _need_cuda(weight, "weight")
+    if weight.dim() != 3:
+        raise ValueError("pointnerf_amd: weight must be [R, SR, K], got %s" % (list(weight.shape),))
+    R, SR, K = (int(x) for x in weight.shape)
+    f32, i32 = torch.float32, torch.int32
+    _dense_arg(blend_w, "blend_w", f32, R * SR); _dense_arg(weight, "weight", f32, R * SR * K)
+    _dense_arg(sample_pidx, "sample_pidx", i32, R * SR * K); _dense_arg(ray_hit, "ray_hit", i32, R)
+    for name, t in (("blend_w", blend_w), ("sample_pidx", sample_pidx), ("ray_hit", ray_hit)):
+        if t.device != weight.device:
+            raise ValueError("pointnerf_amd: %s is on %s, weight on %s" % (name, t.device, weight.device))
+    return R, SR, K
+
+
+def ray_attributes(attr, blend_w, weight, sample_pidx, ray_hit, n_points=None):
+    """pnerf_ray_attributes: a per-point table seen through the render, and the point behind every ray, from the renderer's dense tensors
+    (blend_w [R,SR], weight [R,SR,K], sample_pidx [R,SR,K] i32, ray_hit [R] i32 as render_dense leaves them), one launch, no host read.
+    With g[r,s,k] = blend_w[r,s] * weight[r,s,k] (0 where sample_pidx is outside [0, n_points): the empty slot -1 reads no point; the
+    confidence factor of the density is not part of g) and ``attr`` [n_points, C] float32, C <= 256:
+      attr_sum [R, C] = sum_{s,k} g attr[sample_pidx]  (fp32, fixed order, no atomics: two calls give the same bits);
+      top_flat [R] i32 = the lowest flat index s*K + k among the maxima of g[r] -- the largest single (sample, slot) entry, not a per-point
+      sum over the ray's samples --, top_point [R] i32 = sample_pidx there, top_contrib [R] = g there; -1 / -1 / 0 where no g is > 0.
+    Rays that missed get zeros and -1.  ``n_points`` (default: the rows of ``attr``) may be smaller than the table.  ``attr`` = None runs the
+    pick only (attr_sum is [R, 0]); without ``n_points`` every index >= 0 then counts."""
+    R, SR, K = _ray_entries(blend_w, weight, sample_pidx, ray_hit)
+    f32, i32, dev = torch.float32, torch.int32, weight.device
+    C = 0
+    if attr is not None:
+        _need_cuda(attr, "attr")
+        if attr.dim() != 2:
+            raise ValueError("pointnerf_amd: attr must be [n_points, C], got %s" % (list(attr.shape),))
+        _dense_arg(attr, "attr", f32)
+        n_points, C = int(attr.shape[0]) if n_points is None else int(n_points), int(attr.shape[1])
+        if n_points > int(attr.shape[0]):
+            raise ValueError("pointnerf_amd: n_points %d exceeds the %d rows of attr" % (n_points, int(attr.shape[0])))
+        if C > RAY_ATTRIBUTES_CMAX:
+            raise ValueError("pointnerf_amd: attr has %d columns, pnerf_ray_attributes takes at most %d" % (C, RAY_ATTRIBUTES_CMAX))
+    elif n_points is None:
+        n_points = 2 ** 31 - 1                                            # no table to stay inside: every index >= 0 counts
+    out = dict(attr_sum=torch.empty(R, C, dtype=f32, device=dev), top_point=torch.empty(R, dtype=i32, device=dev),
+               top_flat=torch.empty(R, dtype=i32, device=dev), top_contrib=torch.empty(R, dtype=f32, device=dev))
+    L.check(L.lib().pnerf_ray_attributes(_ptr(attr if C else None), int(n_points), C, _ptr(blend_w), _ptr(weight), _ptr(sample_pidx), _ptr(ray_hit),
+                                         R, SR, K, _ptr(out["attr_sum"] if C else None), _ptr(out["top_point"]), _ptr(out["top_flat"]),
+                                         _ptr(out["top_contrib"]), _stream()), "pnerf_ray_attributes")
+    return out
+
+
+def lift_to_points(values, ray_factor, blend_w, weight, sample_pidx, ray_hit, n_points, out=None):
+    """pnerf_lift_to_points, the adjoint of ray_attributes: per-ray ``values`` [R, C] float32 (C <= 8; None: C = 0) times the optional per-ray
+    factor ``ray_factor`` [R] float32 (None: 1) spread onto the points with the same g: point_sum[p, c] += g m[r] values[r, c],
+    point_mass[p] += g m[r] over every entry that addresses p.  Returns (point_sum [n_points, C], point_mass [n_points]); ``out`` = None
+    allocates zeroed accumulators, ``out`` = (point_sum, point_mass) ADDS into the caller's, so that several views add up.  The sums are
+    fp32 atomicAdd on global memory (like the backward's point gradients): they depend on arrival order and are NOT bit-reproducible."""
+    R, SR, K = _ray_entries(blend_w, weight, sample_pidx, ray_hit)
+    f32, dev, n_points = torch.float32, weight.device, int(n_points)
+    C = 0
+    if values is not None:
+        _need_cuda(values, "values")
+        if values.dim() != 2:
+            raise ValueError("pointnerf_amd: values must be [R, C], got %s" % (list(values.shape),))
+        C = int(values.shape[1])
+        if C > LIFT_CMAX:
+            raise ValueError("pointnerf_amd: values has %d columns, pnerf_lift_to_points takes at most %d" % (C, LIFT_CMAX))
+        _dense_arg(values, "values", f32, R * C)
+    if ray_factor is not None:
+        _dense_arg(ray_factor, "ray_factor", f32, R)
+    if out is None:
+        out = (torch.zeros(n_points, C, dtype=f32, device=dev), torch.zeros(n_points, dtype=f32, device=dev))
+    point_sum, point_mass = out
+    _need_cuda(point_sum, "out[0]")
+    if point_sum.dim() != 2 or int(point_sum.shape[1]) != C:
+        raise ValueError("pointnerf_amd: out[0] must be [n_points, %d], got %s" % (C, list(point_sum.shape)))
+    _dense_arg(point_sum, "out[0]", f32, n_points * C); _dense_arg(point_mass, "out[1]", f32, n_points)
+    L.check(L.lib().pnerf_lift_to_points(_ptr(values if C else None), C, _ptr(ray_factor), _ptr(blend_w), _ptr(weight), _ptr(sample_pidx), _ptr(ray_hit),
+                                         R, SR, K, n_points, _ptr(point_sum if C else None), _ptr(point_mass), _stream()), "pnerf_lift_to_points")
+    return point_sum, point_mass
+
+
 # ------------------------------------------------------------------------------------------ profiling
 def mfma_rate_tflops(mode=2, ms_target=60.0, device=None):
     """TFLOP/s of register-resident v_mfma_f32_32x32x16_f16 on the whole chip (pnerf_debug_mfma_rate; mode 0 zero operands, 1 one constant,
