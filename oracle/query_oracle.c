@@ -25,8 +25,11 @@
  *
  * Arithmetic: fp32, no FMA contraction (build with -ffp-contract=off), IEEE
  * division.  Overflow of max_o or P is where the reference switches to a
- * wall-clock seeded curand reservoir (parity undefined); here it is detected and
- * reported in info[] and the overflowing item is dropped.
+ * wall-clock seeded curand reservoir; here it is detected and reported in info[]
+ * and the overflowing item is dropped.  For P that is the reference's own result
+ * whenever its draws replace nothing (the serial host build of oracle/_ref, whose
+ * uniform numbers are all 1): the first P points of a cell by index are kept, and
+ * tests/test_oracle_query.py pins it.  Past max_o parity stays undefined.
  */
 #include <math.h>
 #include <stdint.h>

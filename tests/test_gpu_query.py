@@ -67,6 +67,59 @@ def test_native_op_edge_cases():
         _assert_same(q, *_native_op(opt, xyz, inp, q["hp"]))
 
 
+def _query_case_names():
+    import query_case
+    return query_case.NAMES
+
+
+@pytest.mark.parametrize("name", _query_case_names())
+def test_query_cases_native_op_bit_exact(name):
+    """tests/query_case.py through woord_query_grid_point_index: per-axis query_size / vsize / vscale / kernel_size / ranges (family A), more
+    points in a cell than P (B: the first P by index are kept), points and samples on cell boundaries with tied distances (C; incl. K = 16,
+    which has no reference pin).  The device decides what the emulated kernels cannot: how grid.hip / query.hip divide and whether they contract."""
+    import query_case as QC
+    QC.conditions(name)
+    QC.check(name, DEV)
+
+
+@pytest.mark.parametrize("name", [n for n in _query_case_names() if n[0] in "AB"])
+def test_query_cases_fused_ray_generation(name):
+    """families A and B through lighting_fast_querier.query_dense: grid_hyperparameters from the points on the device, rays generated inside
+    k_probe<false, false>.  Hit rays, samples and indices equal the oracle's, n_occ and max_cnt of the grid equal the oracle's, and overflow_P
+    is reported where (and only where) a cell holds more than P points: in all of family B, and in the three s2 cases of family A whose
+    fullest cell holds 14 or 15 points"""
+    import query_case as QC
+    QC.conditions(name)
+    QC.check_dense(name, DEV)
+
+
+def test_max_o_overflow_is_reported_and_changes_nothing():
+    """the brick map of grid.hip has no use for max_o (every occupied cell is kept): with max_o below the number of occupied cells the outputs
+    are those of max_o = 50000 and overflow_max_o is reported.  No oracle comparison: parity past max_o is undefined (config.bench_lego_opt)."""
+    import copy
+    import query_case as QC
+    from pointnerf_amd.point_query import lighting_fast_querier
+    name = "A/all/s2"
+    c, n_occ = QC.build(name), QC.oracle(name)["info"]["n_occ"]
+    assert n_occ > 100
+    xd = c.xyz.to(DEV)
+    res = {}
+    for max_o in (50000, n_occ // 2):
+        opt = copy.copy(c.opt)
+        opt.max_o = max_o
+        qr = lighting_fast_querier(torch.device(DEV), opt)
+        dense = qr.query_dense(xd[None], c.xyz.shape[0], 2.0, 6.0, c.inp["raydir"].to(DEV), c.inp["campos"].to(DEV))
+        res[max_o] = ({k: v.cpu() for k, v in dense.items()}, qr.last_grid_info, qr.last_grid)
+    (a, ga, grid_a), (b, gb, grid_b) = res[50000], res[n_occ // 2]
+    assert grid_a is not grid_b and grid_b.gp.max_o == n_occ // 2
+    assert ga["overflow_max_o"] is False and gb["overflow_max_o"] is True and gb["n_occ"] == n_occ == ga["n_occ"]
+    assert int(a["counters"][3]) > 50
+    for k in ("sample_pidx", "sample_loc", "sample_nn", "ray_hit", "counters"):
+        assert torch.equal(a[k], b[k]), k
+    n_valid = int(a["counters"][0])
+    assert torch.equal(a["valid_list"][:n_valid], b["valid_list"][:n_valid])
+
+
 def test_querier_config1_chair():
     """BASELINE.json configs[0] through lighting_fast_querier.query_points (fused ray generation)."""
     from pointnerf_amd.point_query import lighting_fast_querier

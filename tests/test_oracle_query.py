@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from pointnerf_amd import config, scenes
+import query_case
 from oracle import pyref, query as oq
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_query.npz")
@@ -20,6 +21,10 @@ _golden = {}
 
 
 def _ref(case, opt, xyz, inp):
+    return _ref_of(case, lambda: pyref.query(opt, xyz, inp, impl="ref"))
+
+
+def _ref_of(case, run_live):
     """the reference kernels' query result for `case`: live where oracle/_ref can be built (and then equal to the recording), else the recording"""
     if _RECORD is None and not _golden:
         with np.load(GOLDEN) as z:
@@ -31,7 +36,7 @@ def _ref(case, opt, xyz, inp):
         ray_mask=torch.from_numpy(_golden[case + "/ray_mask"]), info={"curand_hits": int(_golden[case + "/curand_hits"])})
     if not oq.have_ref():
         return rec
-    live = pyref.query(opt, xyz, inp, impl="ref")
+    live = run_live()
     if _RECORD is not None:
         _RECORD[case] = live
     else:
@@ -101,6 +106,26 @@ def test_edge_cases_match_reference():
     _same(pyref.query(opt, xyz, inp, impl="oracle"), _ref("edge_no_radius", opt, xyz, inp))
 
 
+@pytest.mark.parametrize("name", query_case.REF_NAMES)
+def test_query_cases_equal_reference_kernels(name):
+    """tests/query_case.py against the reference's own kernels: per-axis sizes (family A), P overflow (B), lattice points and samples on cell
+    boundaries with tied distances (C, the K <= 8 cases: the reference's K-buffer holds 8).
+    Where a cell holds more than P points the reference draws a uniform number for every further point (curand_hits > 0) and turns it into a
+    slot between 0 and the cell's count so far; the point replaces a kept one when that slot is below P (query_worldcoords.cu:152-158).  The
+    serial host build's shim returns u = 1, the slot is the count itself (>= P) and nothing is replaced: the first P points by index stay, in
+    canonical serial order.  That is one of the outcomes the reference itself
+    can produce (its seed is the wall clock), it is the rule of grid.hip (pn_cell_points: min(P, count) of the index-sorted cell), and the
+    recording of it is as canonical as the others."""
+    fig = query_case.conditions(name)
+    a = query_case.oracle(name)
+    b = _ref_of("qc/" + name, lambda: query_case.reference(name))
+    print(name, fig, "curand_hits", b["info"]["curand_hits"])
+    assert (b["info"]["curand_hits"] > 0) == (a["info"]["ovf_P"] == 1)
+    if name in query_case.OVERFLOWS_P:
+        assert b["info"]["curand_hits"] > 0
+    query_case.check(name, lambda _: (b["sample_pidx"], b["sample_loc_w"], b["ray_mask"]))
+
+
 def test_voxel0_quirk_is_reproduced():
     """query_worldcoords.cu:147 `voxel_idx > 0`: the cell of the first in-range point holds no points."""
     opt, xyz, inp = _scene(0, 1200)
@@ -161,6 +186,8 @@ if __name__ == "__main__":
         test_oracle_equals_reference_kernels(*sc)
     test_config1_chair_equals_reference_kernels()
     test_edge_cases_match_reference()
+    for name in query_case.REF_NAMES:
+        test_query_cases_equal_reference_kernels(name)
     out = {}
     for case, r in _RECORD.items():
         out.update({case + "/sample_pidx": r["sample_pidx"].numpy(), case + "/sample_loc_w": r["sample_loc_w"].numpy(),
