@@ -18,7 +18,7 @@
 //
 // Compiled with -ffp-contract=off: the cell arithmetic must round exactly like the reference's.
 #include <limits.h>
-#include "pn_common.h"
+#include "pn_ray.h"
 
 PnGridLayout pn_grid_layout(const pnerf_grid_params *gp, int n) {
     PnGridLayout L;
@@ -112,9 +112,10 @@ __global__ __launch_bounds__(TPB) void k_brick_bits(long long NB, const int *__r
     if (brick >= NB) return;
     const int c = cnt[brick * 64 + (threadIdx.x & 63)];
     const unsigned long long bits = __ballot(c > 0);
-    int sum = c, mx = c;
+    const int sum = pn_wave_sum(c);
+    int mx = c;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { sum += __shfl_xor(sum, off, 64); mx = max(mx, __shfl_xor(mx, off, 64)); }
+    for (int off = 32; off > 0; off >>= 1) mx = max(mx, __shfl_xor(mx, off, 64));
     if ((threadIdx.x & 63) == 0) {
         bocc[brick] = __popcll(bits);
         bpts[brick] = sum;

@@ -57,7 +57,7 @@ int pn_compact_gt0_i32(const int *in, long long n, int *list, int *count_out, in
 // ---- the zero-one regulariser on one neighbor slot's confidence: THE definition of its arithmetic ----------------------------------
 // conf_coefficient = gradient_clamp(points_conf[clamp(sample_pidx, min=0)], 1e-4, 1) (point_aggregators.py:722-724, 812), loss_zero_one's term
 // log(v) + log(1 - v), v = clamp(conf_coefficient, eps, 1 - eps) (base_rendering_model.py:630-641).  Used by the regulariser's own passes
-// (render.hip) and by the render backward that carries its conf gradient (backward.hip: k_agg_backward, k_zero_one_empty).
+// (loss.hip) and by the render backward that carries its conf gradient (backward.hip: k_agg_backward, k_zero_one_empty).
 __device__ __forceinline__ int pn_zero_one_point(int p, int n) { return p < 0 ? 0 : (p >= n ? n - 1 : p); }       // an empty slot (-1) reads point 0
 struct PnZeroOne {
     float c, eps;            // c: the gradient_clamp'ed confidence (clamp forward, identity backward)

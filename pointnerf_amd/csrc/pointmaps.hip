@@ -20,19 +20,14 @@
 // entries, keeps the column sums in registers, a point row is one 4..16-byte read per lane, butterfly sums at the end); the general C <= 256
 // is column-parallel in passes of 64 columns (lane c owns a column, the K slots of a sample arrive by lane broadcast, a point row is one
 // coalesced read).  A sample with blend_w == 0 (an empty slot, a sample a cut render left unshaded, a miss) is skipped before its rows are
-// read.  The shuffle helpers are restatements of render.hip's file-local ones: that file is not touched.
-#include "pn_common.h"
+// read.  The butterfly sum and the order of the pick are pn_ray.h's (pn_wave_sum, PnWaveArgmax); the pick carries the point index as a
+// third word through its butterfly (re-reading sample_pidx at the winner instead measured 2-3 % slower: profiles/HISTORY.md).
+#include "pn_ray.h"
 
 namespace {
 constexpr int PN_PM_TPB = 256;       // 4 rays per workgroup
 constexpr int PN_PM_CMAX = 256;      // k_ray_attributes: columns of the attribute table
 constexpr int PN_PM_LIFT_CMAX = 8;   // k_lift_to_points: columns of the per-ray values
-
-__device__ __forceinline__ float pm_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 struct PmIn {
     const float *blend_w, *weight;
@@ -55,25 +50,26 @@ __device__ __forceinline__ float pm_entry(const PmIn &a, long long row, int e, i
     return bw * a.weight[row * a.K + e];
 }
 
+// PnWaveArgmax on (g, flat index) with the entry's point as payload
 struct PmPick {
-    float v; int e, p;
-    __device__ __forceinline__ PmPick() : v(-INFINITY), e(0x7fffffff), p(-1) {}
+    PnWaveArgmax b;
+    int p = -1;
     __device__ __forceinline__ void take(float ov, int oe, int op) {
-        if (ov > v || (ov == v && oe < e)) { v = ov; e = oe; p = op; }
+        if (b.loses_to(ov, oe)) { b.v = ov; b.i = oe; p = op; }
     }
     __device__ __forceinline__ void meet() {                             // every lane ends with the same triple: the order is total
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(v, off, 64);
-            const int oe = __shfl_xor(e, off, 64), op = __shfl_xor(p, off, 64);
+            const float ov = __shfl_xor(b.v, off, 64);
+            const int oe = __shfl_xor(b.i, off, 64), op = __shfl_xor(p, off, 64);
             take(ov, oe, op);
         }
     }
     __device__ __forceinline__ void store(const PmOut &o, long long r) const {
-        const bool any = v > 0.f;                                        // a hit ray whose largest g is not > 0: -1, -1, 0
+        const bool any = b.v > 0.f;                                      // a hit ray whose largest g is not > 0: -1, -1, 0
         o.top_point[r] = any ? p : -1;
-        o.top_flat[r] = any ? e : -1;
-        o.top_contrib[r] = any ? v : 0.f;
+        o.top_flat[r] = any ? b.i : -1;
+        o.top_contrib[r] = any ? b.v : 0.f;
     }
 };
 
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(PN_PM_TPB) void k_ray_attributes(PmIn a, const floa
     best.meet();
     if constexpr (C > 0) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = pm_wave_sum(acc[c]);
+        for (int c = 0; c < C; ++c) acc[c] = pn_wave_sum(acc[c]);
     }
     if (lane == 0) {
         best.store(o, r);

@@ -9,14 +9,14 @@
 // the outputs are full-size and nothing is compacted or scattered afterwards.
 //
 // Shape: one 64-lane wavefront per ray (like k_raymarch_forward), four rays per workgroup, no LDS, no atomics.  The lanes stride over the
-// ray's SR opacities in chunks of 64; the (value, index) pairs meet in one xor butterfly whose order relation -- larger value first, then
-// the smaller index -- is total, so every lane ends with the same pair whatever the tree and the result is the LOWEST index among the
-// maxima.  Lane k < K then owns neighbor slot k (point index, weight, distance); in the averages lane c owns an output column (0..31 the
+// ray's SR opacities in chunks of 64; the (value, index) pairs meet in PnWaveArgmax (pn_ray.h), whose order relation -- larger value
+// first, then the smaller index -- is total, so every lane ends with the same pair whatever the tree and the result is the LOWEST index
+// among the maxima.  Lane k < K then owns neighbor slot k (point index, weight, distance); in the averages lane c owns an output column (0..31 the
 // embedding: a point row is one coalesced 128-byte read of 32 lanes; 32..34 colour, 35..37 direction, 38 confidence) and the K slots
 // arrive by lane broadcast.  The pass is latency- and HBM-bound: SR opacities plus K point rows per hit ray.
 //
 // k_probe_hole_mask restates the candidate rule of probe_hole (run/train_ft.py:489-500, with bloat_inds :532-540) per pixel of a view.
-#include "pn_common.h"
+#include "pn_ray.h"
 
 namespace {
 constexpr int PN_PR_TPB = 256;       // k_probe_rays: 4 rays per workgroup
@@ -50,19 +50,10 @@ __global__ __launch_bounds__(PN_PR_TPB) void k_probe_rays(PrPoints pts, const fl
     }
     // ---- s* = the lowest index among the maxima of opacity[r, 0 .. SR-1]   (torch.max(dim=-1), :331)
     const float *op = opacity + r * SR;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int s = lane; s < SR; s += 64) {
-        const float v = op[s];
-        if (v > bv || (v == bv && s < bi)) { bv = v; bi = s; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off, 64);
-        const int oi = __shfl_xor(bi, off, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    const int ss = bi < SR ? bi : 0;                         // (a row of NaN compares false everywhere: stay inside the row)
+    PnWaveArgmax best;
+    for (int s = lane; s < SR; s += 64) best.take(op[s], s);
+    best.meet();
+    const int ss = best.i < SR ? best.i : 0;                         // (a row of NaN compares false everywhere: stay inside the row)
     const long long smp = r * SR + ss;
     const float mx = op[ss];
     const float lx = sample_loc[smp * 3], ly = sample_loc[smp * 3 + 1], lz = sample_loc[smp * 3 + 2];       // :333-334

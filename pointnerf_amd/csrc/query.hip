@@ -22,7 +22,7 @@
 //     device-built work list of the valid samples.
 // Compiled with -ffp-contract=off (cell arithmetic and squared distances must round like the
 // reference: left-to-right fp32, no FMA).
-#include "pn_common.h"
+#include "pn_ray.h"
 
 #ifndef PN_NB_BATCH
 #define PN_NB_BATCH 4
@@ -212,8 +212,7 @@ __global__ __launch_bounds__(TPB) void k_ray_hit(int R, int SR, const int *__res
     for (int r = r0; r < r0 + RAYS_PER_WAVE && r < R; ++r) {
         int nb = 0;
         for (int s = lane; s < SR; s += 64) nb += sample_nn[(size_t)r * SR + s];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) nb += __shfl_xor(nb, off, 64);
+        nb = pn_wave_sum(nb);
         if (lane == 0) {
             ray_hit[r] = nb > 0;
             hits += nb > 0; sel += sel_cnt[r]; nbs += nb;

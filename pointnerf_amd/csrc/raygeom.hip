@@ -6,38 +6,23 @@
 // already uses (raydir is not normalised, so z IS the ray parameter up to the pixel's constant); blend weight, opacity and transmittance
 // are ray_march's (models/rendering/diff_ray_marching.py:508-554) as k_raymarch_forward (render.hip) forms them: opacity and blend_w are
 // READ BACK from the renderer's outputs, not recomputed, and the inclusive transmittance T_s = prod_{j <= s} (1 - op_j + 1e-10) is a
-// wave-inclusive product per 64-slot chunk times the product carried over the chunks in front.  Per ray:
+// wave-inclusive product per 64-slot chunk times the product carried over the chunks in front (PnTransmittance, pn_ray.h).  Per ray:
 //   acc = sum_s bw_s      depth_sum = sum_s bw_s z_s (valid slots only)      depth = depth_sum / (acc + 1e-6)
 //   median_slot = the lowest valid slot with T_s < 0.5 (-1: none),   median_depth = z there (0: none)
 // A ray that missed the cloud gets zeros and -1; its rows are not read.
 //
 // Shape: one 64-lane wavefront per ray (like k_raymarch_forward / k_probe_rays), four rays per workgroup, no LDS, no atomics.  The lanes
 // stride over SR in chunks of 64 and keep per-lane partial sums over the chunks; lanes at or beyond SR carry neutral elements (u = 1,
-// bw = 0).  The sums meet in the xor butterfly of render.hip's wave_sum, so the accumulation order is a function of SR alone and two calls
+// bw = 0).  The sums meet in the xor butterfly of pn_wave_sum (pn_ray.h), so the accumulation order is a function of SR alone and two calls
 // give the same bits.  The pass is HBM-bound: 24 bytes per slot (sample_loc, sample_nn, opacity, blend_w) against the ray march's ~44.
-// The shuffle helpers are restatements of render.hip's file-local ones: that file is not touched.
+// The wave scans, the perspective depth and the transmittance step are pn_ray.h's, the ones the ray march itself runs.
 //
 // k_geometry_canvas: the per-pixel fill of the three maps for one chunk of rays (one thread per ray), instead of three index-puts.
-#include "pn_common.h"
+#include "pn_ray.h"
 
 namespace {
 constexpr int PN_RG_TPB = 256;       // k_ray_geometry: 4 rays per workgroup
 constexpr int PN_GC_TPB = 256;
-
-__device__ __forceinline__ float rg_wave_incl_prod(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v *= y; }
-    return v;
-}
-__device__ __forceinline__ float rg_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-// perspective depth of a world position: ((p - campos) @ camrot)[2]   (point_query.py:101-108)
-__device__ __forceinline__ float rg_pers_z(const pnerf_camera &c, const float *p) {
-    return (p[0] - c.campos[0]) * c.camrot[2] + (p[1] - c.campos[1]) * c.camrot[5] + (p[2] - c.campos[2]) * c.camrot[8];
-}
 
 struct RgArgs {
     pnerf_camera cam;
@@ -60,30 +45,29 @@ __global__ __launch_bounds__(PN_RG_TPB) void k_ray_geometry(RgArgs a, RgOut o) {
     }
     const int SR = a.SR;
     const long long row = r * SR;
-    float T_carry = 1.f, sum_w = 0.f, sum_wz = 0.f, mz = 0.f;
+    PnTransmittance tr;
+    float sum_w = 0.f, sum_wz = 0.f, mz = 0.f;
     int ms = -1;
     for (int base = 0; base < SR; base += 64) {
         const int s = base + lane;
         const bool in = s < SR;
         const bool valid = in && a.nn[row + s] > 0;                      // ray_valid = any_K(mask)  point_aggregators.py:741
-        const float z = valid ? rg_pers_z(a.cam, a.sample_loc + (row + s) * 3) : 0.f;       // an empty slot's position is never read
+        const float z = valid ? pn_pers_z(a.cam, a.sample_loc + (row + s) * 3) : 0.f;       // an empty slot's position is never read
         const float op = in ? a.opacity[row + s] : 0.f;
         const float bw = in ? a.blend_w[row + s] : 0.f;                  // (0 on the empty slots: the renderer wrote it)
         sum_w += bw;
         sum_wz += bw * z;
-        const float u = in ? (1.f - op + 1e-10f) : 1.f;                  // diff_ray_marching.py:533
-        const float incl = rg_wave_incl_prod(u, lane);
-        const float Tin = incl * T_carry;                                // transmittance BEHIND slot s
+        float Tx;
+        const float Tin = tr.step(op, in, lane, Tx);                     // transmittance BEHIND slot s  (diff_ray_marching.py:533)
         const unsigned long long below = __ballot(valid && Tin < 0.5f);
         if (ms < 0 && below != 0ull) {                                   // (wave-uniform)  the first crossing: the lowest lane of the lowest chunk
             const int first = __ffsll((long long)below) - 1;
             ms = base + first;
             mz = __shfl(z, first, 64);
         }
-        T_carry *= __shfl(incl, 63, 64);
     }
-    sum_w = rg_wave_sum(sum_w);
-    sum_wz = rg_wave_sum(sum_wz);
+    sum_w = pn_wave_sum(sum_w);
+    sum_wz = pn_wave_sum(sum_wz);
     if (lane == 0) {
         o.acc[r] = sum_w;
         o.depth_sum[r] = sum_wz;

@@ -1,14 +1,15 @@
-// render.hip -- ray-dist + alpha-composite volume renderer (forward and backward) and the C-ABI entry
-// points of the fused render path.
+// render.hip -- ray-dist + alpha-composite volume renderer (forward and backward), the cut render, and the C-ABI entry points of the
+// fused render path.
 //
 // Replaces the ray_dist block of NeuralPointsRayMarching.forward
 // (models/neural_points_volumetric_model.py:271-279) and ray_march
 // (models/rendering/diff_ray_marching.py:508-554; radiance_render / alpha_blend / no_tone_map,
 // models/rendering/diff_render_func.py:36-62).  One 64-lane wavefront per ray: the cummax over the
-// perspective depth and the exclusive transmittance product are wave scans (shuffle), no intermediate
+// perspective depth and the exclusive transmittance product are wave scans (pn_ray.h), no intermediate
 // [R,SR] tensors of the reference (sigma, opacity, cumprod, blend weight, ...) are materialised except
 // the ones the caller asks for.
 #include "mlp_common.h"
+#include "pn_ray.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -22,53 +23,17 @@ struct RmArgs {
     int R, SR;
 };
 
-__device__ __forceinline__ float wave_incl_max(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v = fmaxf(v, y); }
-    return v;
-}
-__device__ __forceinline__ float wave_incl_prod(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v *= y; }
-    return v;
-}
-__device__ __forceinline__ float wave_incl_sum(float v, int lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v += y; }
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// perspective depth of a world position: ((p - campos) @ camrot)[2]   (point_query.py:101-108)
-__device__ __forceinline__ float pers_z(const pnerf_camera &c, const float *p) {
-    return (p[0] - c.campos[0]) * c.camrot[2] + (p[1] - c.campos[1]) * c.camrot[5] + (p[2] - c.campos[2]) * c.camrot[8];
-}
-
 // Per-sample quantities of one 64-sample chunk of a ray.  `cm_prev` is the running cummax before the
 // chunk.  Returns delta (ray_dist), valid flag, and updates cm_prev.
 __device__ __forceinline__ void chunk_raydist(const RmArgs &a, int r, int s, int lane, float &cm_prev, float &delta, bool &valid) {
     const int SR = a.SR;
+    const long long row = (long long)r * SR;
     if (a.ray_dist) {
-        valid = s < SR && a.valid8[(long long)r * SR + s] != 0;
-        delta = s < SR ? a.ray_dist[(long long)r * SR + s] : 0.f;
+        valid = s < SR && a.valid8[row + s] != 0;
+        delta = s < SR ? a.ray_dist[row + s] : 0.f;
         return;
     }
-    float z = -INFINITY, znext = -INFINITY;
-    if (s < SR) z = pers_z(a.cam, a.sample_loc + ((long long)r * SR + s) * 3);
-    if (s + 1 < SR) znext = pers_z(a.cam, a.sample_loc + ((long long)r * SR + s + 1) * 3);
-    float cm = fmaxf(wave_incl_max(z, lane), cm_prev);             // torch.cummax(sample_loc[...,2])  :271
-    const float vs = a.cam.vsize_z;
-    float d = (s + 1 < SR) ? fmaxf(cm, znext) - cm : vs;            // cm[s+1] - cm[s]; last = vsize[2]   :272
-    bool m = d < 1e-8f;
-    if (a.cam.raydist_mode_unit > 0) m = m || (d > 2.f * vs);       // :274-276
-    if (m) d = vs;                                                  // :278
-    valid = s < SR && a.nn[(long long)r * SR + s] > 0;              // ray_valid = any_K(mask)  point_aggregators.py:741
-    delta = valid ? d : 0.f;                                        // :279
-    cm_prev = __shfl(cm, 63, 64);
+    pn_chunk_raydist(a.cam, a.sample_loc, a.nn, row, s, SR, SR, lane, cm_prev, delta, valid);
 }
 
 __global__ __launch_bounds__(TPB) void k_raymarch_forward(RmArgs a, float *__restrict__ ray_color, float *__restrict__ opacity_out,
@@ -78,7 +43,8 @@ __global__ __launch_bounds__(TPB) void k_raymarch_forward(RmArgs a, float *__res
     const int r = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
     if (r >= a.R) return;
     const int SR = a.SR;
-    float cm_prev = -INFINITY, T_carry = 1.f;
+    float cm_prev = -INFINITY;
+    PnTransmittance tr;
     float cr = 0.f, cg = 0.f, cb = 0.f;
     for (int base = 0; base < SR; base += 64) {
         const int s = base + lane;
@@ -90,11 +56,8 @@ __global__ __launch_bounds__(TPB) void k_raymarch_forward(RmArgs a, float *__res
             sigma = valid ? f.x : 0.f; rr = f.y; gg = f.z; bb = f.w;
         }
         const float op = 1.f - expf(-sigma * delta);                    // diff_ray_marching.py:530
-        const float u = s < SR ? (1.f - op + 1e-10f) : 1.f;             // :533
-        const float incl = wave_incl_prod(u, lane);
-        float Tx = __shfl_up(incl, 1, 64);                              // exclusive product by lane shift   :533-539
-        if (lane == 0) Tx = 1.f;
-        Tx *= T_carry;
+        float Tx;
+        tr.step(op, s < SR, lane, Tx);
         const float bw = op * Tx;                                       // alpha_blend
         if (s < SR) {
             opacity_out[(long long)r * SR + s] = op;
@@ -102,13 +65,13 @@ __global__ __launch_bounds__(TPB) void k_raymarch_forward(RmArgs a, float *__res
             if (acc_trans) acc_trans[(long long)r * SR + s] = Tx;
         }
         cr += bw * rr; cg += bw * gg; cb += bw * bb;
-        T_carry *= __shfl(incl, 63, 64);
     }
-    cr = wave_sum(cr); cg = wave_sum(cg); cb = wave_sum(cb);
+    const float T_end = tr.T_carry;
+    cr = pn_wave_sum(cr); cg = pn_wave_sum(cg); cb = pn_wave_sum(cb);
     if (lane == 0) {
-        if (a.cam.has_bg) { cr += a.cam.bg[0] * T_carry; cg += a.cam.bg[1] * T_carry; cb += a.cam.bg[2] * T_carry; }   // :543-545
+        if (a.cam.has_bg) { cr += a.cam.bg[0] * T_end; cg += a.cam.bg[1] * T_end; cb += a.cam.bg[2] * T_end; }   // :543-545
         ray_color[3 * r] = cr; ray_color[3 * r + 1] = cg; ray_color[3 * r + 2] = cb;
-        bg_trans[r] = T_carry;
+        bg_trans[r] = T_end;
     }
 }
 
@@ -122,7 +85,8 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
     const int SR = a.SR;
     const float g0 = grad_color[3 * r], g1 = grad_color[3 * r + 1], g2 = grad_color[3 * r + 2];
     // pass 1: T_end and total = sum_j bw_j (g . rgb_j)
-    float cm_prev = -INFINITY, T_carry = 1.f, tot = 0.f;
+    float cm_prev = -INFINITY, tot = 0.f;
+    PnTransmittance tr;
     for (int base = 0; base < SR; base += 64) {
         const int s = base + lane;
         float delta; bool valid;
@@ -133,19 +97,15 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
             sigma = valid ? f.x : 0.f; c = g0 * f.y + g1 * f.z + g2 * f.w;
         }
         const float op = 1.f - expf(-sigma * delta);
-        const float u = s < SR ? (1.f - op + 1e-10f) : 1.f;
-        const float incl = wave_incl_prod(u, lane);
-        float Tx = __shfl_up(incl, 1, 64);
-        if (lane == 0) Tx = 1.f;
-        Tx *= T_carry;
+        float Tx;
+        tr.step(op, s < SR, lane, Tx);
         tot += op * Tx * c;
-        T_carry *= __shfl(incl, 63, 64);
     }
-    tot = wave_sum(tot);
-    const float T_end = T_carry;
+    tot = pn_wave_sum(tot);
+    const float T_end = tr.T_carry;
     const float gbg = a.cam.has_bg ? (g0 * a.cam.bg[0] + g1 * a.cam.bg[1] + g2 * a.cam.bg[2]) * T_end : 0.f;
     // pass 2: per-sample gradients with the running prefix of bw_j c_j
-    cm_prev = -INFINITY; T_carry = 1.f;
+    cm_prev = -INFINITY; tr = PnTransmittance();
     float pre_carry = 0.f;
     for (int base = 0; base < SR; base += 64) {
         const int s = base + lane;
@@ -158,13 +118,11 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
         }
         const float e = expf(-sigma * delta);
         const float op = 1.f - e;
-        const float u = s < SR ? (1.f - op + 1e-10f) : 1.f;
-        const float incl = wave_incl_prod(u, lane);
-        float Tx = __shfl_up(incl, 1, 64);
-        if (lane == 0) Tx = 1.f;
-        Tx *= T_carry;
+        const float u = PnTransmittance::u_of(op, s < SR);
+        float Tx;
+        tr.step(op, s < SR, lane, Tx);
         const float bwc = op * Tx * c;
-        const float incl_sum = wave_incl_sum(bwc, lane) + pre_carry;      // sum_{j<=s}
+        const float incl_sum = pn_wave_incl_sum(bwc, lane) + pre_carry;   // sum_{j<=s}
         const float suffix = tot - incl_sum + gbg;                        // sum_{j>s} bw_j c_j + T_end (g.bg)
         const float dop = Tx * c - suffix / u;
         if (s < SR) {
@@ -175,15 +133,15 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
             *reinterpret_cast<float4 *>(grad_decoded + ((long long)r * SR + s) * 4) = o;
         }
         pre_carry = __shfl(incl_sum, 63, 64);
-        T_carry *= __shfl(incl, 63, 64);
     }
 }
 
 // ---- early ray termination of a render-only pass ("cut render", include/pnerf.h: pnerf_render_forward_cut) -------------------------
 // The reference has no counterpart for the cut itself; what is thresholded is ray_march's transmittance (models/rendering/
-// diff_ray_marching.py:508-554) as k_raymarch_forward forms it: the ray-dist deltas of chunk_raydist, u = 1 - op + 1e-10, the product
-// over the slots in front.  A ray is shaded front to back in stages of B slots; the step of stage j advances the ray's transmittance
-// through the slots of stage j - 1 (their sigma is in `decoded` by then; unshaded samples hold 0), drops the ray once T < cutoff, and
+// diff_ray_marching.py:508-554) as k_raymarch_forward forms it: the ray-dist deltas of pn_chunk_raydist and the transmittance step of
+// PnTransmittance (pn_ray.h), the very code the ray march runs, so an uncut ray matches pnerf_render_forward bit for bit.  A ray is
+// shaded front to back in stages of B slots; the step of stage j advances the ray's transmittance through the slots of stage j - 1 (their
+// sigma is in `decoded` by then; unshaded samples hold 0), drops the ray once T < cutoff, and
 // flags the slots of stage j with a neighbor of the rays still alive.  One wavefront per ray.  Per-ray state between stages: the running
 // T, the running cummax of the perspective depth in front of the next slot to advance through (the ray-dist delta needs it), and
 //   alive: 1 = still shaded, 0 = a miss or ended with nothing left to shade, 2 = ended with at least one valid sample unshaded
@@ -203,32 +161,21 @@ __global__ __launch_bounds__(TPB) void k_cut_stage(CutArgs a, float *__restrict_
     const int SR = a.SR;
     const long long row = (long long)r * SR;
     int alive;
-    float T = 1.f, cm_prev = -INFINITY;
+    PnTransmittance tr;
+    float cm_prev = -INFINITY;
     if (a.stage == 0) alive = (!a.hit || a.hit[r] > 0) ? 1 : 0;      // (no hit flags: a ray without a valid sample flags nothing and keeps T = 1)
     else {
-        alive = alive_st[r]; T = T_st[r]; cm_prev = cm_st[r];
+        alive = alive_st[r]; tr.T_carry = T_st[r]; cm_prev = cm_st[r];
         if (alive == 1) {
             const int s0 = (a.stage - 1) * a.B, s1 = s0 + a.B;             // the previous stage's slots (s1 < SR: this stage exists)
-            const float vs = a.cam.vsize_z;
             for (int base = s0; base < s1; base += 64) {                   // B need not divide 64: lanes beyond s1 carry neutral elements
                 const int s = base + lane;
-                const bool in = s < s1;
-                float z = -INFINITY, znext = -INFINITY;
-                if (in) z = pers_z(a.cam, a.sample_loc + (row + s) * 3);
-                if (in && s + 1 < SR) znext = pers_z(a.cam, a.sample_loc + (row + s + 1) * 3);
-                const float cm = fmaxf(wave_incl_max(z, lane), cm_prev);   // as chunk_raydist
-                float d = (s + 1 < SR) ? fmaxf(cm, znext) - cm : vs;
-                bool m = d < 1e-8f;
-                if (a.cam.raydist_mode_unit > 0) m = m || (d > 2.f * vs);
-                if (m) d = vs;
-                const bool valid = in && a.nn[row + s] > 0;
+                float delta, Tx; bool valid;
+                pn_chunk_raydist(a.cam, a.sample_loc, a.nn, row, s, s1, SR, lane, cm_prev, delta, valid);
                 const float sigma = valid ? a.decoded[(row + s) * 4] : 0.f;
-                const float op = 1.f - expf(-sigma * (valid ? d : 0.f));
-                const float u = in ? (1.f - op + 1e-10f) : 1.f;
-                T *= __shfl(wave_incl_prod(u, lane), 63, 64);
-                cm_prev = __shfl(cm, 63, 64);
+                tr.step(1.f - expf(-sigma * delta), s < s1, lane, Tx);
             }
-            if (!(T >= a.cutoff)) {                                        // the ray ends here: does that leave a valid sample unshaded?
+            if (!(tr.T_carry >= a.cutoff)) {                               // the ray ends here: does that leave a valid sample unshaded?
                 int left = 0;
                 for (int base = s1; base < SR; base += 64) {
                     const int s = base + lane;
@@ -238,7 +185,7 @@ __global__ __launch_bounds__(TPB) void k_cut_stage(CutArgs a, float *__restrict_
             }
         }
     }
-    if (lane == 0) { T_st[r] = T; cm_st[r] = cm_prev; alive_st[r] = alive; }
+    if (lane == 0) { T_st[r] = tr.T_carry; cm_st[r] = cm_prev; alive_st[r] = alive; }
     const int f0 = a.stage * a.B, f1 = f0 + a.B;
     for (int base = 0; base < SR; base += 64) {                            // the whole row: the compaction reads every flag
         const int s = base + lane;
@@ -252,8 +199,7 @@ __global__ __launch_bounds__(1024) void k_cut_totals(const int *__restrict__ sta
     __shared__ int red[16];
     int n = 0;
     for (int r = threadIdx.x; r < R; r += 1024) n += alive_st[r] == 2 ? 1 : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
+    n = pn_wave_sum(n);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -263,251 +209,7 @@ __global__ __launch_bounds__(1024) void k_cut_totals(const int *__restrict__ sta
         out[0] = shaded; out[1] = cut; out[2] = 0; out[3] = 0;
     }
 }
-
-// ---- row gather / scatter-add (NeuralPoints.forward's index_select and its backward) -----------
-__global__ __launch_bounds__(TPB) void k_gather_rows(const float *__restrict__ src, int n_src, int width, const int *__restrict__ idx,
-                                                     long long n_idx, float *__restrict__ dst) {
-    const long long total = n_idx * width;
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += (long long)gridDim.x * TPB) {
-        const long long i = e / width;
-        const int c = (int)(e - i * width);
-        int p = idx[i];
-        p = p < 0 ? 0 : (p >= n_src ? n_src - 1 : p);         // torch.clamp(sample_pidx, min=0)  neural_points.py:708
-        dst[e] = src[(long long)p * width + c];
-    }
-}
-// width a multiple of 4 with width / 4 a power of two <= 64 (the embedding: 32 floats = 8 lanes x 16 bytes per row): a group of W4 lanes copies one
-// row with 16-byte accesses, no per-element division.  (Round 3's 4.2 TB/s for this kernel came from the loop vectoriser, which the library has
-// had switched off since round 4 -- the packed-fp32 fault, csrc/Makefile --: the scalar form above fell to 3.1 TB/s; profiles/r0[345]_microbench.json.)
-template <int W4>
-__global__ __launch_bounds__(TPB) void k_gather_rows_v4(const float4 *__restrict__ src, int n_src, const int *__restrict__ idx, long long n_idx, float4 *__restrict__ dst) {
-    const int c = threadIdx.x & (W4 - 1);
-    for (long long i = ((long long)blockIdx.x * TPB + threadIdx.x) / W4; i < n_idx; i += (long long)gridDim.x * (TPB / W4)) {
-        int p = idx[i];
-        p = p < 0 ? 0 : (p >= n_src ? n_src - 1 : p);
-        const float4 v = src[(long long)p * W4 + c];
-        pn_f4 t = {v.x, v.y, v.z, v.w};
-        __builtin_nontemporal_store(t, reinterpret_cast<pn_f4 *>(dst + i * W4 + c));
-    }
-}
-// -1 slots were gathered from point 0 (A.9 of SURVEY.md: the reference lets point 0 collect gradient from every
-// empty slot).  Those are the vast majority of the slots, all hitting ONE row: they are summed per block in LDS
-// first and leave as one atomic per column per block; real indices go straight to global atomics.
-__global__ __launch_bounds__(TPB) void k_scatter_add_rows(const float *__restrict__ grad_rows, const int *__restrict__ idx, long long n_idx,
-                                                          int width, float *__restrict__ grad_src, int n_src) {
-    __shared__ float row0[64];
-    const bool use_lds = width <= 64;
-    if (use_lds && threadIdx.x < 64) row0[threadIdx.x] = 0.f;
-    __syncthreads();
-    const long long total = n_idx * width;
-    for (long long e = (long long)blockIdx.x * TPB + threadIdx.x; e < total; e += (long long)gridDim.x * TPB) {
-        const long long i = e / width;
-        const int c = (int)(e - i * width);
-        int p = idx[i];
-        const float g = grad_rows[e];
-        if (p <= 0 && use_lds) { atomicAdd(&row0[c], g); continue; }
-        p = p < 0 ? 0 : (p >= n_src ? n_src - 1 : p);
-        atomicAdd(&grad_src[(long long)p * width + c], g);
-    }
-    __syncthreads();
-    if (use_lds && threadIdx.x < width && row0[threadIdx.x] != 0.f) atomicAdd(&grad_src[threadIdx.x], row0[threadIdx.x]);
-}
-
-// ---- the zero-one regulariser on the confidences of the hit rays' neighbor slots, fused --------------------------------------------
-// Reference: conf_coefficient = gradient_clamp(points_conf[clamp(sample_pidx, min=0)], 1e-4, 1) (point_aggregators.py:722-724, 812) and
-// loss_zero_one = mean(log(v) + log(1 - v)), v = clamp(conf_coefficient, eps, 1 - eps) (base_rendering_model.py:630-641): a gather, two
-// clamps, two logs, a reduction and their autograd mirror over [R'', SR, K] elements (84 M at configs[3]) -- ~20 element-wise passes
-// in ATen.  Here: one pass that sums the terms per block (the caller adds the per-block partials: deterministic), one pass that
-// adds  g * (1 / v - 1 / (1 - v)) [eps <= c' <= 1 - eps]  into the confidence gradient, with the point-0 flood of the empty slots
-//  reduced per block first.
-// One forward and one backward kernel over rows x slots elements of the index table, a workgroup per row at a time.  The rays form: rows = R,
-// slots = SR * K, hit = the per-ray hit flags (only rays that hit the cloud count: the reference forms conf_coefficient for the R'' hit rays
-// only; no [R'', SR, K] copy of the table is ever made).  The flat form: rows of TPB elements, hit = NULL, `total` cuts the last row short.
-__global__ __launch_bounds__(TPB) void k_zero_one_forward(const float *__restrict__ conf, int n, const int *__restrict__ idx, const int *__restrict__ hit, long long rows, int slots,
-                                                          long long total, float eps, float *__restrict__ partial) {
-    __shared__ float red[TPB / 64];
-    float acc = 0.f;
-    for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
-        if (hit && hit[r] <= 0) continue;
-        const int *row = idx + r * slots;
-        const int m = (int)(total - r * slots < slots ? total - r * slots : slots);
-        for (int e = threadIdx.x; e < m; e += TPB) acc += PnZeroOne(conf[pn_zero_one_point(row[e], n)], eps).value();
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int w = 0; w < TPB / 64; ++w) t += red[w];
-        partial[blockIdx.x] = t;
-    }
-}
-__global__ __launch_bounds__(TPB) void k_zero_one_backward(const float *__restrict__ conf, int n, const int *__restrict__ idx, const int *__restrict__ hit, long long rows, int slots,
-                                                           long long total, float eps, const float *__restrict__ gscale, float *__restrict__ grad_conf) {
-    __shared__ float row0;
-    if (threadIdx.x == 0) row0 = 0.f;
-    __syncthreads();
-    const float gs = gscale[0];
-    float mine0 = 0.f;
-    for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
-        if (hit && hit[r] <= 0) continue;
-        const int *row = idx + r * slots;
-        const int m = (int)(total - r * slots < slots ? total - r * slots : slots);
-        for (int e = threadIdx.x; e < m; e += TPB) {
-            const int p = pn_zero_one_point(row[e], n);
-            const PnZeroOne z(conf[p], eps);
-            if (!z.inside()) continue;
-            if (p == 0) mine0 += z.grad(gs);
-            else atomicAdd(&grad_conf[p], z.grad(gs));
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine0 += __shfl_xor(mine0, off, 64);
-    if ((threadIdx.x & 63) == 0 && mine0 != 0.f) atomicAdd(&row0, mine0);
-    __syncthreads();
-    if (threadIdx.x == 0 && row0 != 0.f) atomicAdd(&grad_conf[0], row0);
-}
 }  // namespace
-
-namespace {
-// colour term of the training loss over the DENSE ray colours with the rays' hit flags (models/base_rendering_model.py:543-551:
-// ray_masked_coarse_raycolor = sum over the hit rays' (colour - gt)^2, the caller divides by its global element count): no compaction of the
-// hit rays (argsort + index_selects) on the way to a scalar.  partial[b] = block sums; backward writes d colour for EVERY ray (0 for a miss),
-// which is what the renderer's backward reads.
-__global__ __launch_bounds__(256) void k_color_loss_forward_rays(const float *__restrict__ col, const float *__restrict__ gt, const int *__restrict__ hit, int R,
-                                                                 float *__restrict__ partial) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (int r = blockIdx.x * 256 + threadIdx.x; r < R; r += gridDim.x * 256)
-        if (hit[r] > 0) {
-            const float dx = col[3 * r] - gt[3 * r], dy = col[3 * r + 1] - gt[3 * r + 1], dz = col[3 * r + 2] - gt[3 * r + 2];
-            acc += (dx * dx + dy * dy) + dz * dz;
-        }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-__global__ __launch_bounds__(256) void k_color_loss_backward_rays(const float *__restrict__ col, const float *__restrict__ gt, const int *__restrict__ hit, int R,
-                                                                  const float *__restrict__ gscale, float *__restrict__ gcol) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= R) return;
-    const float g = hit[r] > 0 ? 2.f * gscale[0] : 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gcol[3 * r + c] = g == 0.f ? 0.f : g * (col[3 * r + c] - gt[3 * r + c]);
-}
-}  // namespace
-extern "C" int pnerf_color_loss_blocks(int R) {
-    const int b = (R + 255) / 256;
-    return b < 1 ? 1 : (b > 1024 ? 1024 : b);
-}
-extern "C" int pnerf_color_loss_forward_rays(const float *d_ray_color, const float *d_gt, const int32_t *d_ray_hit, int R, float *d_partial, void *stream) {
-    if (!d_ray_color || !d_gt || !d_ray_hit || !d_partial || R < 0) return PNERF_E_INVAL;
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_color_loss_forward_rays, dim3(pnerf_color_loss_blocks(R)), dim3(256), 0, (hipStream_t)stream, d_ray_color, d_gt, d_ray_hit, R, d_partial);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int pnerf_color_loss_backward_rays(const float *d_ray_color, const float *d_gt, const int32_t *d_ray_hit, int R, const float *d_gscale,
-                                              float *d_grad_ray_color, void *stream) {
-    if (R == 0) return 0;
-    if (!d_ray_color || !d_gt || !d_ray_hit || !d_gscale || !d_grad_ray_color || R < 0) return PNERF_E_INVAL;
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_color_loss_backward_rays, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_ray_color, d_gt, d_ray_hit, R, d_gscale, d_grad_ray_color);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pnerf_zero_one_blocks(int64_t n_idx) {
-    const long long b = (n_idx + TPB - 1) / TPB;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-// both passes of both forms: rows x slots elements of d_idx (`total` of them exist), d_hit optional; the caller has checked its arguments
-static int pn_zero_one_launch(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_hit, long long rows, int slots, long long total, float eps,
-                              float *d_partial, const float *d_gscale, float *d_grad_conf, void *stream) {
-    const dim3 grid(pnerf_zero_one_blocks(rows * TPB));
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    if (d_partial) hipLaunchKernelGGL(k_zero_one_forward, grid, dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, d_hit, rows, slots, total, eps, d_partial);
-    else hipLaunchKernelGGL(k_zero_one_backward, grid, dim3(TPB), 0, (hipStream_t)stream, d_conf, n_points, d_idx, d_hit, rows, slots, total, eps, d_gscale, d_grad_conf);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
-extern "C" int pnerf_zero_one_forward_rays(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_ray_hit, int R, int slots_per_ray, float eps,
-                                           float *d_partial, void *stream) {
-    if (!d_conf || !d_partial || !d_idx || !d_ray_hit || n_points <= 0 || R < 0 || slots_per_ray <= 0) return PNERF_E_INVAL;
-    return pn_zero_one_launch(d_conf, n_points, d_idx, d_ray_hit, R, slots_per_ray, (long long)R * slots_per_ray, eps, d_partial, nullptr, nullptr, stream);
-}
-extern "C" int pnerf_zero_one_backward_rays(const float *d_conf, int n_points, const int32_t *d_idx, const int32_t *d_ray_hit, int R, int slots_per_ray, float eps,
-                                            const float *d_gscale, float *d_grad_conf, void *stream) {
-    if (R == 0) return 0;
-    if (!d_conf || !d_idx || !d_ray_hit || !d_gscale || !d_grad_conf || n_points <= 0 || R < 0 || slots_per_ray <= 0) return PNERF_E_INVAL;
-    return pn_zero_one_launch(d_conf, n_points, d_idx, d_ray_hit, R, slots_per_ray, (long long)R * slots_per_ray, eps, nullptr, d_gscale, d_grad_conf, stream);
-}
-extern "C" int pnerf_zero_one_forward(const float *d_conf, int n_points, const int32_t *d_idx, int64_t n_idx, float eps, float *d_partial, void *stream) {
-    if (!d_conf || !d_partial || n_points <= 0 || n_idx < 0 || (n_idx > 0 && !d_idx)) return PNERF_E_INVAL;
-    return pn_zero_one_launch(d_conf, n_points, d_idx, nullptr, (n_idx + TPB - 1) / TPB, TPB, n_idx, eps, d_partial, nullptr, nullptr, stream);
-}
-extern "C" int pnerf_zero_one_backward(const float *d_conf, int n_points, const int32_t *d_idx, int64_t n_idx, float eps, const float *d_gscale,
-                                       float *d_grad_conf, void *stream) {
-    if (n_idx == 0) return 0;
-    if (!d_conf || !d_idx || !d_gscale || !d_grad_conf || n_points <= 0 || n_idx < 0) return PNERF_E_INVAL;
-    return pn_zero_one_launch(d_conf, n_points, d_idx, nullptr, (n_idx + TPB - 1) / TPB, TPB, n_idx, eps, nullptr, d_gscale, d_grad_conf, stream);
-}
-
-extern "C" int pnerf_gather_rows(const float *d_src, int n_src, int width, const int32_t *d_idx, int64_t n_idx, float *d_dst, void *stream) {
-    if (n_idx == 0) return 0;                      // nothing to gather (a chunk of rays that hit nothing): pointers may be null
-    if (!d_src || !d_idx || !d_dst || n_src <= 0 || width <= 0 || n_idx < 0) return PNERF_E_INVAL;
-    long long total = n_idx * width;
-    int grid = (int)((total + TPB - 1) / TPB < 16384 ? (total + TPB - 1) / TPB : 16384);
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    const bool al = ((uintptr_t)d_src % 16 == 0) && ((uintptr_t)d_dst % 16 == 0);
-    const long long rows_per_block = TPB / (width / 4 > 0 ? width / 4 : 1);
-    const int gridv = (int)((n_idx + rows_per_block - 1) / rows_per_block < 16384 ? (n_idx + rows_per_block - 1) / rows_per_block : 16384);
-    if (al && width == 32) hipLaunchKernelGGL(k_gather_rows_v4<8>, dim3(gridv), dim3(TPB), 0, (hipStream_t)stream, (const float4 *)d_src, n_src, d_idx, (long long)n_idx, (float4 *)d_dst);
-    else if (al && width == 4) hipLaunchKernelGGL(k_gather_rows_v4<1>, dim3(gridv), dim3(TPB), 0, (hipStream_t)stream, (const float4 *)d_src, n_src, d_idx, (long long)n_idx, (float4 *)d_dst);
-    else hipLaunchKernelGGL(k_gather_rows, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, d_src, n_src, width, d_idx, (long long)n_idx, d_dst);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pnerf_scatter_add_rows(const float *d_grad_rows, const int32_t *d_idx, int64_t n_idx, int width, float *d_grad_src, int n_src, void *stream) {
-    if (n_idx == 0) return 0;
-    if (!d_grad_rows || !d_idx || !d_grad_src || n_src <= 0 || width <= 0 || n_idx < 0) return PNERF_E_INVAL;
-    long long total = n_idx * width;
-    int grid = (int)((total + TPB - 1) / TPB < 4096 ? (total + TPB - 1) / TPB : 4096);
-    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_scatter_add_rows, dim3(grid), dim3(TPB), 0, (hipStream_t)stream, d_grad_rows, d_idx, (long long)n_idx, width, d_grad_src, n_src);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
-
-// flags[p] = 1 for every point p that occurs in the neighbor table, flags[0] = 1 if any slot is empty (empty slots read point 0 like the
-// reference, neural_points.py:709, and the zero-one regulariser differentiates through that read): the rows a rank's point gradients can be
-// non-zero in -- what a data-parallel caller exchanges instead of the dense [N, 39] gradient (pointnerf_amd/dist.py).  Plain stores of the
-// same value race benignly; the table is read as int4 where it can be.
-namespace {
-__global__ __launch_bounds__(256) void k_touched_flags(const int *__restrict__ pidx, long long n, int n_points, int *__restrict__ flags) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int p = pidx[i];
-        if (p >= 0 && p < n_points) flags[p] = 1;
-        else if (p < 0) flags[0] = 1;
-    }
-}
-}  // namespace
-extern "C" int pnerf_touched_flags(const int32_t *d_pidx, int64_t n, int32_t n_points, int32_t *d_flags, void *stream) {
-    if (n < 0 || n_points < 0 || (n > 0 && !d_pidx) || (n_points > 0 && !d_flags)) return PNERF_E_INVAL;
-    hipStream_t s = (hipStream_t)stream;
-    if (n_points == 0) return 0;
-    if (hipMemsetAsync(d_flags, 0, (size_t)n_points * sizeof(int32_t), s) != hipSuccess) return PNERF_E_LAUNCH;
-    if (n == 0) return 0;
-    const long long blocks = (n + 255) / 256;
-    PnProfScope prof(PNK_GATHER, s);
-    hipLaunchKernelGGL(k_touched_flags, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, s, d_pidx, (long long)n, n_points, d_flags);
-    PN_CHECK_LAUNCH();
-    return 0;
-}
 
 // the argument of the two ray-march kernels, in its two forms: ray distances and validity from the camera, the samples' positions and their
 // neighbor counts (the fused path), or supplied by the caller with the background colour (the stand-alone ray_march())

@@ -69,6 +69,24 @@ def _dense_arg(t, name, dtype, numel=None):
     return t
 
 
+def _dense_args(anchor_name, anchor, *specs):
+    """_dense_arg on every (name, tensor, dtype, numel) of ``specs``, in their order; then, with an anchor, every tensor must be on the anchor's
+    device (anchor_name = None: no device check)"""
+    for name, t, dtype, numel in specs:
+        _dense_arg(t, name, dtype, numel)
+    if anchor_name is not None:
+        for name, t, _, _ in specs:
+            if t.device != anchor.device:
+                raise ValueError("pointnerf_amd: %s is on %s, %s on %s" % (name, t.device, anchor_name, anchor.device))
+
+
+def _render_outputs(R, SR, K, device):
+    """the six results of a render forward, uninitialised: decoded, weight, ray_color, opacity, bg_trans, blend_w"""
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.empty(R, SR, 4, **f32), torch.empty(R, SR, K, **f32), torch.empty(R, 3, **f32), torch.empty(R, SR, **f32),
+            torch.empty(R, **f32), torch.empty(R, SR, **f32))
+
+
 # ------------------------------------------------------------------------------------------ grid
 def mid_depths(D, near, far):
     """The D mid-point depths of near_far_linear_ray_generation with jitter=0
@@ -411,10 +429,7 @@ def render_forward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, tra
     """pnerf_render_forward.  n_valid = host copy of dense['counters'][0] (capacity of the scratch).
     Returns dict(decoded, weight, ray_color, opacity, bg_trans, blend_w, saved)."""
     dev = raydir.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    decoded = torch.empty(R, SR, 4, **f32); weight = torch.empty(R, SR, K, **f32)
-    ray_color = torch.empty(R, 3, **f32); opacity = torch.empty(R, SR, **f32)
-    bg_trans = torch.empty(R, **f32); blend_w = torch.empty(R, SR, **f32)
+    decoded, weight, ray_color, opacity, bg_trans, blend_w = _render_outputs(R, SR, K, dev)
     st = make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
     saved, ws, nws = _forward_scratch(n_valid, K, train, dev)
     L.check(L.lib().pnerf_render_forward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st),
@@ -444,10 +459,7 @@ def render_forward_cut(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid,
     cutoff, stage = check_cutoff(cutoff, stage)
     lib = L.lib()
     dev = raydir.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    decoded = torch.empty(R, SR, 4, **f32); weight = torch.empty(R, SR, K, **f32)
-    ray_color = torch.empty(R, 3, **f32); opacity = torch.empty(R, SR, **f32)
-    bg_trans = torch.empty(R, **f32); blend_w = torch.empty(R, SR, **f32)
+    decoded, weight, ray_color, opacity, bg_trans, blend_w = _render_outputs(R, SR, K, dev)
     cut_counters = torch.empty(4, dtype=torch.int32, device=dev)
     st = make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
     _, ws, nws = _forward_scratch(n_valid, K, False, dev)
@@ -466,8 +478,8 @@ def cut_stage(cam, sample_loc, sample_nn, ray_hit, decoded, cutoff, stage_sample
     dict(trans [R], depth_max [R], alive [R] i32 -- the per-ray state, updated in place --, flags [R,SR] i32, list, counters [8] i32)."""
     R, SR = int(sample_nn.shape[0]), int(sample_nn.shape[1])
     f32, i32 = torch.float32, torch.int32
-    _dense_arg(sample_loc, "sample_loc", f32, R * SR * 3); _dense_arg(sample_nn, "sample_nn", i32, R * SR)
-    _dense_arg(ray_hit, "ray_hit", i32, R); _dense_arg(decoded, "decoded", f32, R * SR * 4)
+    _dense_args(None, None, ("sample_loc", sample_loc, f32, R * SR * 3), ("sample_nn", sample_nn, i32, R * SR), ("ray_hit", ray_hit, i32, R),
+                ("decoded", decoded, f32, R * SR * 4))
     dev = sample_nn.device
     if state is None:
         state = dict(trans=torch.empty(R, dtype=f32, device=dev), depth_max=torch.empty(R, dtype=f32, device=dev), alive=torch.empty(R, dtype=i32, device=dev))
@@ -746,8 +758,8 @@ def probe_rays(pts, opacity, weight, sample_loc, sample_pidx, ray_hit, R, SR, K)
     each (C = 1, 3, 1, 3, 3, 1, 32 in the order of PROBE_RAY_KEYS); the rows of the rays that missed are zero."""
     R, SR, K = int(R), int(SR), int(K)
     f32, i32 = torch.float32, torch.int32
-    _dense_arg(opacity, "opacity", f32, R * SR); _dense_arg(weight, "weight", f32, R * SR * K); _dense_arg(sample_loc, "sample_loc", f32, R * SR * 3)
-    _dense_arg(sample_pidx, "sample_pidx", i32, R * SR * K); _dense_arg(ray_hit, "ray_hit", i32, R)
+    _dense_args(None, None, ("opacity", opacity, f32, R * SR), ("weight", weight, f32, R * SR * K), ("sample_loc", sample_loc, f32, R * SR * 3),
+                ("sample_pidx", sample_pidx, i32, R * SR * K), ("ray_hit", ray_hit, i32, R))
     out = {k: torch.empty(R, c, dtype=f32, device=opacity.device) for k, c in PROBE_RAY_KEYS}
     L.check(L.lib().pnerf_probe_rays(ctypes.byref(pts), _ptr(opacity), _ptr(weight), _ptr(sample_loc), _ptr(sample_pidx), _ptr(ray_hit), R, SR, K,
                                      *[_ptr(out[k]) for k, _ in PROBE_RAY_KEYS], _stream()), "pnerf_probe_rays")
@@ -790,12 +802,9 @@ def ray_geometry(cam, sample_loc, sample_nn, ray_hit, opacity, blend_w):
         raise ValueError("pointnerf_amd: sample_nn must be [R, SR], got %s" % (list(sample_nn.shape),))
     R, SR = int(sample_nn.shape[0]), int(sample_nn.shape[1])
     f32, i32 = torch.float32, torch.int32
-    _dense_arg(sample_loc, "sample_loc", f32, R * SR * 3); _dense_arg(sample_nn, "sample_nn", i32, R * SR); _dense_arg(ray_hit, "ray_hit", i32, R)
-    _dense_arg(opacity, "opacity", f32, R * SR); _dense_arg(blend_w, "blend_w", f32, R * SR)
+    _dense_args("sample_nn", sample_nn, ("sample_loc", sample_loc, f32, R * SR * 3), ("sample_nn", sample_nn, i32, R * SR), ("ray_hit", ray_hit, i32, R),
+                ("opacity", opacity, f32, R * SR), ("blend_w", blend_w, f32, R * SR))
     dev = sample_nn.device
-    for name, t in (("sample_loc", sample_loc), ("ray_hit", ray_hit), ("opacity", opacity), ("blend_w", blend_w)):
-        if t.device != dev:
-            raise ValueError("pointnerf_amd: %s is on %s, sample_nn on %s" % (name, t.device, dev))
     rows = torch.empty(4, R, dtype=f32, device=dev)
     out = {k: rows[i] for i, k in enumerate(RAY_GEOMETRY_KEYS[:4])}
     out["median_slot"] = torch.empty(R, dtype=i32, device=dev)
@@ -858,11 +867,8 @@ def _ray_entries(blend_w, weight, sample_pidx, ray_hit):
         raise ValueError("pointnerf_amd: weight must be [R, SR, K], got %s" % (list(weight.shape),))
     R, SR, K = (int(x) for x in weight.shape)
     f32, i32 = torch.float32, torch.int32
-    _dense_arg(blend_w, "blend_w", f32, R * SR); _dense_arg(weight, "weight", f32, R * SR * K)
-    _dense_arg(sample_pidx, "sample_pidx", i32, R * SR * K); _dense_arg(ray_hit, "ray_hit", i32, R)
-    for name, t in (("blend_w", blend_w), ("sample_pidx", sample_pidx), ("ray_hit", ray_hit)):
-        if t.device != weight.device:
-            raise ValueError("pointnerf_amd: %s is on %s, weight on %s" % (name, t.device, weight.device))
+    _dense_args("weight", weight, ("blend_w", blend_w, f32, R * SR), ("weight", weight, f32, R * SR * K), ("sample_pidx", sample_pidx, i32, R * SR * K),
+                ("ray_hit", ray_hit, i32, R))
     return R, SR, K
 
 

@@ -1,4 +1,4 @@
-"""The unified zero-one pass (one forward / one backward kernel over rows x slots, csrc/render.hip) in its two forms -- the flat index list
+"""The unified zero-one pass (one forward / one backward kernel over rows x slots, csrc/loss.hip) in its two forms -- the flat index list
 (ops.zero_one_conf_sum) and the dense neighbor table with hit flags (ops.zero_one_conf_sum_rays) -- against the ATen chain it replaces:
 gather with the -1 -> point 0 rule, gradient_clamp, clamp(eps, 1 - eps), log + log(1 - .), sum.  Shared by the emulator test
 (tests/test_emu_kernels.py) and the device test (tests/test_gpu_level1.py): same shapes, each with the bars of its neighbour test there.
