@@ -344,7 +344,10 @@ int pnerf_agg_backward(const pnerf_camera *cam, const pnerf_points *pts, const p
                        void *d_saved, float *d_grad_params, const pnerf_point_grads *pg, void *d_ws, size_t ws_bytes, void *stream);
 
 /* ray_march(ray_dist, ray_valid, ray_features, radiance, alpha, bg) (models/rendering/diff_ray_marching.py:508-554):
- * d_ray_dist [R,SR] f32, d_ray_valid [R,SR] u8, d_features [R,SR,4] (sigma,r,g,b), bg3_host NULL = no background. */
+ * d_ray_dist [R,SR] f32, d_ray_valid [R,SR] u8, d_features [R,SR,4] (sigma,r,g,b), bg3_host NULL = no background.
+ * PNERF_E_INVAL: a null pointer other than bg3_host, R < 0, SR <= 0.  R == 0: nothing is enqueued.  The backward keeps one lane per
+ * 64-slot chunk of a ray: SR > 4096 -> PNERF_E_UNSUP, from pnerf_raymarch_backward and from pnerf_render_backward (the reference's
+ * largest SR is 400). */
 int pnerf_raymarch_forward(const float *d_ray_dist, const uint8_t *d_ray_valid, const float *d_features, const float *bg3_host,
                            int R, int SR, float *d_ray_color, float *d_opacity, float *d_acc_trans, float *d_blend_w,
                            float *d_bg_trans, void *stream);

@@ -22,15 +22,24 @@ __device__ __forceinline__ float pn_wave_incl_max(float v, int lane) {
     for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v = fmaxf(v, y); }
     return v;
 }
-__device__ __forceinline__ float pn_wave_incl_prod(float v, int lane) {
+template <class F> __device__ __forceinline__ F pn_wave_incl_prod(F v, int lane) {                   // F = float, or double (the ray-march backward)
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v *= y; }
+    for (int off = 1; off < 64; off <<= 1) { F y = __shfl_up(v, off, 64); if (lane >= off) v *= y; }
     return v;
 }
 __device__ __forceinline__ float pn_wave_incl_sum(float v, int lane) {
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) { float y = __shfl_up(v, off, 64); if (lane >= off) v += y; }
     return v;
+}
+// back to front, over the maps x -> a x + b: lane l ends with f_l o f_(l+1) o ... o f_63, the map that carries a value from behind lane 63
+// to in front of lane l (a = 1, b = 0 is the neutral element)
+__device__ __forceinline__ void pn_wave_rincl_affine(double &a, double &b, int lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double oa = __shfl_down(a, off, 64), ob = __shfl_down(b, off, 64);
+        if (lane + off < 64) { b = a * ob + b; a *= oa; }
+    }
 }
 
 // perspective depth of a world position: ((p - campos) @ camrot)[2]   (point_query.py:101-108)
@@ -61,21 +70,23 @@ __device__ __forceinline__ void pn_chunk_raydist(const pnerf_camera &cam, const 
 }
 
 // ray_march's transmittance (models/rendering/diff_ray_marching.py:533-539) across the chunks of a ray: u = 1 - op + 1e-10 per slot (1 on a
-// lane outside the ray), T in front of a slot = the product of u over the slots in front of it.
-struct PnTransmittance {
-    float T_carry = 1.f;             // the product over the chunks in front; after the last chunk: the ray's background transmittance
+// lane outside the ray), T in front of a slot = the product of u over the slots in front of it.  F = float: the forward's T, bit for bit, in
+// every kernel that thresholds or stores it; F = double: the same fp32 factors u multiplied without a rounding of their own (the backward).
+template <class F> struct PnTransmittanceT {
+    F T_carry = 1;                   // the product over the chunks in front; after the last chunk: the ray's background transmittance
     static __device__ __forceinline__ float u_of(float op, bool in) { return in ? (1.f - op + 1e-10f) : 1.f; }       // :533
     // one chunk: Tx = the transmittance IN FRONT of the lane's slot (exclusive product by lane shift), returns the one BEHIND it (inclusive)
-    __device__ __forceinline__ float step(float op, bool in, int lane, float &Tx) {
-        const float incl = pn_wave_incl_prod(u_of(op, in), lane);
+    __device__ __forceinline__ F step(float op, bool in, int lane, F &Tx) {
+        const F incl = pn_wave_incl_prod((F)u_of(op, in), lane);
         Tx = __shfl_up(incl, 1, 64);
-        if (lane == 0) Tx = 1.f;
+        if (lane == 0) Tx = 1;
         Tx *= T_carry;
-        const float Tin = incl * T_carry;
+        const F Tin = incl * T_carry;
         T_carry *= __shfl(incl, 63, 64);
         return Tin;
     }
 };
+using PnTransmittance = PnTransmittanceT<float>;
 
 // (largest value, lowest index) over a wave.  The order -- larger value first, then the smaller index -- is total, so after meet() every lane
 // holds the same pair whatever the tree; a NaN compares false everywhere and is never taken.

@@ -78,61 +78,84 @@ __global__ __launch_bounds__(TPB) void k_raymarch_forward(RmArgs a, float *__res
 // Backward: dL/d(ray_color) -> dL/d(decoded) = (d sigma, d r, d g, d b) per sample.
 //   color = sum_s bw_s rgb_s + bg T_end ;  bw_s = op_s T_s ; T_s = prod_{j<s} u_j ; u = 1 - op + eps ; op = 1 - exp(-sigma delta)
 //   d color / d op_s = T_s rgb_s - (sum_{j>s} bw_j rgb_j + T_end bg) / u_s
+// With c_j = g . rgb_j and T_(s+1) = T_s u_s the bracket is T_(s+1) S_s, where S_s is what the ray shows BEHIND slot s, seen from there:
+//   S_(SR-1) = g . bg ;  S_(j-1) = op_j c_j + u_j S_j        so        d (g . color) / d op_s = T_s (c_s - S_s).
+// S is built back to front from the slots behind s alone, by a scan over the maps S -> u_j S + op_j c_j (pn_wave_rincl_affine).  The bracket
+// is never formed as (total - prefix) and nothing is divided by u_s: behind an opaque slot the true bracket is tiny against the ray's total,
+// the difference would keep the rounding residue of the whole ray, and 1 / u_s ~ 1e6 .. 1e10 would blow it up to the size of the ray's own
+// d sigma.  Nor are T_s c_s and the bracket rounded apart before they cancel: the rounding of T_s multiplies the whole difference.
+// Pass 1 leaves the map of chunk i in lane i (one lane per 64-slot chunk: SR <= RM_BWD_MAX_SR) and applies those back to front to g . bg, which
+// gives S behind every chunk; pass 2 runs the transmittance front to back and S back to front within the chunk.
+// delta, op = 1 - expf(-sigma delta) and u are the forward's own fp32 values (chunk_raydist, PnTransmittance::u_of): the gradient is the one of
+// the function the forward evaluates.  What is BUILT from them -- c, the maps, S, T -- is carried in double and rounded once per output, so the
+// order of the wave scans (a tree per lane, whose roundings neighbouring lanes do not share) costs nothing: measured per ray against float64,
+// d sigma and d rgb are as close as the fp32 autograd of the same formula or closer where the device's expf is not what limits them
+// (tests/raymarch_case.py; figures in DESIGN.md 4.9).
+constexpr int RM_BWD_MAX_SR = 64 * 64;
 __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float *__restrict__ grad_color, float *__restrict__ grad_decoded) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
     if (r >= a.R) return;
     const int SR = a.SR;
     const float g0 = grad_color[3 * r], g1 = grad_color[3 * r + 1], g2 = grad_color[3 * r + 2];
-    // pass 1: T_end and total = sum_j bw_j (g . rgb_j)
-    float cm_prev = -INFINITY, tot = 0.f;
-    PnTransmittance tr;
+    // pass 1: in lane i the map of chunk i >= 1, S behind the chunk -> S in front of it (nothing lies in front of chunk 0: its map is not needed)
+    float cm_prev = -INFINITY;
+    double ca = 1., cb = 0.;
     for (int base = 0; base < SR; base += 64) {
         const int s = base + lane;
         float delta; bool valid;
-        chunk_raydist(a, r, s, lane, cm_prev, delta, valid);
-        float sigma = 0.f, c = 0.f;
+        chunk_raydist(a, r, s, lane, cm_prev, delta, valid);              // chunk 0 too: it carries the depth cummax through the ray
+        if (base == 0) continue;
+        float sigma = 0.f;
+        double c = 0.;
         if (s < SR) {
             const float4 f = *reinterpret_cast<const float4 *>(a.decoded + ((long long)r * SR + s) * 4);
-            sigma = valid ? f.x : 0.f; c = g0 * f.y + g1 * f.z + g2 * f.w;
+            sigma = valid ? f.x : 0.f; c = (double)g0 * f.y + (double)g1 * f.z + (double)g2 * f.w;
         }
         const float op = 1.f - expf(-sigma * delta);
-        float Tx;
-        tr.step(op, s < SR, lane, Tx);
-        tot += op * Tx * c;
+        double ma = PnTransmittance::u_of(op, s < SR), mb = op * c;       // a lane outside the ray: u = 1, op c = 0
+        pn_wave_rincl_affine(ma, mb, lane);
+        ma = __shfl(ma, 0, 64); mb = __shfl(mb, 0, 64);
+        if (lane == (base >> 6)) { ca = ma; cb = mb; }
     }
-    tot = pn_wave_sum(tot);
-    const float T_end = tr.T_carry;
-    const float gbg = a.cam.has_bg ? (g0 * a.cam.bg[0] + g1 * a.cam.bg[1] + g2 * a.cam.bg[2]) * T_end : 0.f;
-    // pass 2: per-sample gradients with the running prefix of bw_j c_j
-    cm_prev = -INFINITY; tr = PnTransmittance();
-    float pre_carry = 0.f;
+    // lane i: S BEHIND chunk i -- the background behind the last chunk, then chunk by chunk towards the front
+    const double S_bg = a.cam.has_bg ? (double)g0 * a.cam.bg[0] + (double)g1 * a.cam.bg[1] + (double)g2 * a.cam.bg[2] : 0.;
+    double behind = S_bg, S_front = S_bg;
+    for (int i = (SR - 1) >> 6; i >= 1; --i) {
+        S_front = __shfl(ca, i, 64) * S_front + __shfl(cb, i, 64);        // in front of chunk i = behind chunk i - 1
+        if (lane == i - 1) behind = S_front;
+    }
+    // pass 2: per-sample gradients
+    cm_prev = -INFINITY;
+    PnTransmittanceT<double> tr;
     for (int base = 0; base < SR; base += 64) {
         const int s = base + lane;
         float delta; bool valid;
         chunk_raydist(a, r, s, lane, cm_prev, delta, valid);
-        float sigma = 0.f, c = 0.f;
+        float sigma = 0.f;
+        double c = 0.;
         if (s < SR) {
             const float4 f = *reinterpret_cast<const float4 *>(a.decoded + ((long long)r * SR + s) * 4);
-            sigma = valid ? f.x : 0.f; c = g0 * f.y + g1 * f.z + g2 * f.w;
+            sigma = valid ? f.x : 0.f; c = (double)g0 * f.y + (double)g1 * f.z + (double)g2 * f.w;
         }
         const float e = expf(-sigma * delta);
         const float op = 1.f - e;
         const float u = PnTransmittance::u_of(op, s < SR);
-        float Tx;
+        double Tx;
         tr.step(op, s < SR, lane, Tx);
-        const float bwc = op * Tx * c;
-        const float incl_sum = pn_wave_incl_sum(bwc, lane) + pre_carry;   // sum_{j<=s}
-        const float suffix = tot - incl_sum + gbg;                        // sum_{j>s} bw_j c_j + T_end (g.bg)
-        const float dop = Tx * c - suffix / u;
+        double ma = u, mb = op * c;
+        pn_wave_rincl_affine(ma, mb, lane);
+        const double S_end = __shfl(behind, base >> 6, 64);               // S behind the chunk
+        double S = __shfl_down(ma * S_end + mb, 1, 64);                   // S behind slot s = in front of slot s + 1
+        if (lane == 63) S = S_end;
+        const float dop = (float)(Tx * (c - S));
         if (s < SR) {
-            const float bw = op * Tx;
+            const double bw = op * Tx;
             float4 o;
             o.x = valid ? dop * delta * e : 0.f;                          // d op / d sigma = delta exp(-sigma delta)
-            o.y = bw * g0; o.z = bw * g1; o.w = bw * g2;
+            o.y = (float)(bw * g0); o.z = (float)(bw * g1); o.w = (float)(bw * g2);
             *reinterpret_cast<float4 *>(grad_decoded + ((long long)r * SR + s) * 4) = o;
         }
-        pre_carry = __shfl(incl_sum, 63, 64);
     }
 }
 
@@ -395,6 +418,7 @@ extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points
     if (rc) return rc;
     const int R = st->R, SR = st->SR;
     const size_t gd_bytes = pn_align((size_t)R * SR * 4 * sizeof(float));
+    if (SR > RM_BWD_MAX_SR) return PNERF_E_UNSUP;
     if (ws_bytes < gd_bytes + pn_wgrad_partials_bytes()) return PNERF_E_WS;
     if (R == 0 || st->n_valid_max == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -462,6 +486,7 @@ extern "C" int pnerf_raymarch_forward(const float *d_ray_dist, const uint8_t *d_
 extern "C" int pnerf_raymarch_backward(const float *d_ray_dist, const uint8_t *d_ray_valid, const float *d_features, const float *bg3_host,
                                        int R, int SR, const float *d_grad_ray_color, float *d_grad_features, void *stream) {
     if (!d_ray_dist || !d_ray_valid || !d_features || !d_grad_ray_color || !d_grad_features || R < 0 || SR <= 0) return PNERF_E_INVAL;
+    if (SR > RM_BWD_MAX_SR) return PNERF_E_UNSUP;
     if (R == 0) return 0;
     const RmArgs ra = rm_args(d_ray_dist, d_ray_valid, bg3_host, d_features, R, SR);
     hipStream_t s = (hipStream_t)stream;
