@@ -131,6 +131,21 @@ int pnerf_color_loss_forward_rays(const float *d_ray_color, const float *d_gt, c
 int pnerf_color_loss_backward_rays(const float *d_ray_color, const float *d_gt, const int32_t *d_ray_hit, int R, const float *d_gscale,
                                    float *d_grad_ray_color, void *stream);
 
+/* the depth and the background (mask) terms of the training loss (models/base_rendering_model.py:610-626: l2loss(coarse_depth * gt_mask,
+ * gt_depth * gt_mask) and l2loss(coarse_is_background * (1 - gt_mask), 1 - gt_mask); the caller divides by its global ray count) over the DENSE
+ * per-ray results of a render: d_depth_sum / d_acc [R] as pnerf_ray_geometry wrote them, d_bg_trans [R] as pnerf_render_forward did, the rays'
+ * hit flags, d_gt_depth / d_gt_mask [R].  Per ray, m = gt_mask, d = depth_sum / (acc + 1e-6f) (models/neural_points_volumetric_model.py:321;
+ * the 1 / (acc + 1e-6) of a hit but almost transparent ray is the reference's formula and is kept), T = bg_trans; a ray with d_ray_hit <= 0
+ * counts with d = 0 and T = 1 (fill_invalid's values) and its rows are not read.
+ * forward: d_partial [2 * pnerf_color_loss_blocks(R)]: the block sums of (m (d - gt_depth))^2, then those of ((1 - m) (T - 1))^2.
+ * backward: d_grad_geom [R,3] = the gradient of d_gscale2[0] * (depth numerator) + d_gscale2[1] * (bg numerator) with respect to
+ * (depth_sum, acc, T): g_ds = 2 m^2 (d - gt) / (acc + 1e-6), g_acc = -g_ds d, g_T = 2 (1 - m)^2 (T - 1); zeros for a miss (every element is
+ * written): the d_grad_geom of pnerf_render_backward_geom. */
+int pnerf_geometry_loss_forward_rays(const float *d_depth_sum, const float *d_acc, const float *d_bg_trans, const int32_t *d_ray_hit,
+                                     const float *d_gt_depth, const float *d_gt_mask, int R, float *d_partial, void *stream);
+int pnerf_geometry_loss_backward_rays(const float *d_depth_sum, const float *d_acc, const float *d_bg_trans, const int32_t *d_ray_hit,
+                                      const float *d_gt_depth, const float *d_gt_mask, int R, const float *d_gscale2, float *d_grad_geom, void *stream);
+
 /* ---- aggregator MLP + renderer (PointAggregator.forward/viewmlp,
  * models/aggregators/point_aggregators.py:488-644,727-814; ray-dist,
  * models/neural_points_volumetric_model.py:271-279; ray_march,
@@ -321,6 +336,18 @@ int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, cons
                           const float *d_decoded, const float *d_weight, const float *d_grad_ray_color,
                           void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
                           void *d_ws, size_t ws_bytes, void *stream);
+/* The same backward for a loss that also reads the ray's geometry (the depth and bg loss items of models/base_rendering_model.py:610-626 on
+ * the depth of models/neural_points_volumetric_model.py:318-322 and on ray_march's background transmittance, models/rendering/
+ * diff_ray_marching.py:533-545): d_grad_geom [R,3] = per ray the gradients (g_ds, g_acc, g_T) with respect to pnerf_ray_geometry's
+ * d_depth_sum = sum_s bw_s z_s and d_acc = sum_s bw_s and to pnerf_render_forward's d_bg_trans.  They enter the ray march's backward as
+ * further channels of the colour recurrence (per slot c_s += g_ds z_s + g_acc, per ray g . bg += g_T; z_s = the camera-z depth of the
+ * sample, 0 on an empty slot, whose position is not read), so d sigma arrives at the aggregator's backward with the three terms in it;
+ * sample positions do not depend on the point positions: d xyz has no new term.  d_grad_geom == NULL: pnerf_render_backward, launch for
+ * launch.  Everything else -- checks, workspace, return codes -- as pnerf_render_backward. */
+int pnerf_render_backward_geom(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *step,
+                               const float *d_decoded, const float *d_weight, const float *d_grad_ray_color, const float *d_grad_geom,
+                               void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
+                               void *d_ws, size_t ws_bytes, void *stream);
 
 /* ---- stand-alone (level-1) forms of the same kernels, for callers that use the reference's modules one by one ---- */
 
@@ -353,6 +380,14 @@ int pnerf_raymarch_forward(const float *d_ray_dist, const uint8_t *d_ray_valid, 
                            float *d_bg_trans, void *stream);
 int pnerf_raymarch_backward(const float *d_ray_dist, const uint8_t *d_ray_valid, const float *d_features, const float *bg3_host,
                             int R, int SR, const float *d_grad_ray_color, float *d_grad_features, void *stream);
+/* ray_march's backward for a loss on (ray colour, depth_sum = sum_s blend_weight_s z_s, acc = sum_s blend_weight_s, background transmittance)
+ * (models/rendering/diff_ray_marching.py:508-554; the depth of models/neural_points_volumetric_model.py:318-322): pnerf_raymarch_backward
+ * plus d_z [R,SR] f32, the slots' depths (read on valid slots only), and d_grad_geom [R,3] = (g_ds, g_acc, g_T) per ray.  d sigma gets all
+ * four terms, d rgb is pnerf_raymarch_backward's; with d_grad_geom all zeros so is d sigma.  Checks and return codes as
+ * pnerf_raymarch_backward: PNERF_E_INVAL for a null pointer other than bg3_host, R < 0, SR <= 0; PNERF_E_UNSUP for SR > 4096; R == 0:
+ * nothing is enqueued. */
+int pnerf_raymarch_backward_geom(const float *d_ray_dist, const uint8_t *d_ray_valid, const float *d_features, const float *d_z, const float *bg3_host,
+                                 int R, int SR, const float *d_grad_ray_color, const float *d_grad_geom, float *d_grad_features, void *stream);
 
 /* ---- parameter update: one Adam step of one tensor in one pass (the reference steps two torch.optim.Adam instances,
  * models/mvs_points_volumetric_model.py:80-91 and :98-118; lr / plr, betas (0.9, 0.999), eps 1e-8, no weight decay).

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1005                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1006                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
@@ -159,6 +159,15 @@ PROTOTYPES = {
     "pnerf_prof_collect": (c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64)]),
     # (cam, pts, step, decoded, weight, grad_ray_color, saved, grad_params, pg, ws, ws_bytes, stream)
     "pnerf_render_backward": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(PointGrads), c_void_p, c_size_t, c_void_p]),
+    # (cam, pts, step, decoded, weight, grad_ray_color, grad_geom, saved, grad_params, pg, ws, ws_bytes, stream)
+    "pnerf_render_backward_geom": (c_int, _STEP_ARGS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(PointGrads), c_void_p, c_size_t,
+                                                        c_void_p]),
+    # (ray_dist, ray_valid, features, z, bg3_host, R, SR, grad_ray_color, grad_geom, grad_features, stream)
+    "pnerf_raymarch_backward_geom": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_f32), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (depth_sum, acc, bg_trans, ray_hit, gt_depth, gt_mask, R, partial, stream)
+    "pnerf_geometry_loss_forward_rays": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    # (depth_sum, acc, bg_trans, ray_hit, gt_depth, gt_mask, R, gscale2, grad_geom, stream)
+    "pnerf_geometry_loss_backward_rays": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

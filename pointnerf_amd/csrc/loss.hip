@@ -86,7 +86,78 @@ __global__ __launch_bounds__(256) void k_color_loss_backward_rays(const float *_
 #pragma unroll
     for (int c = 0; c < 3; ++c) gcol[3 * r + c] = g == 0.f ? 0.f : g * (col[3 * r + c] - gt[3 * r + c]);
 }
+
+// depth and mask supervision over the DENSE per-ray geometry of a render (the two loops of models/base_rendering_model.py:610-626:
+// l2loss(coarse_depth * gt_mask, gt_depth * gt_mask) and l2loss(coarse_is_background * (1 - gt_mask), 1 - gt_mask), as numerators -- the
+// caller divides by its global ray count).  Per ray, with m = gt_mask, d = depth_sum / (acc + 1e-6) (models/neural_points_volumetric_model.py:321)
+// and T = the background transmittance; a ray that missed has d = 0 and T = 1, as fill_invalid leaves them:
+//   depth term = (m (d - gt_depth))^2        bg term = ((1 - m) (T - 1))^2
+// partial[b] = block sums of the depth terms, partial[gridDim.x + b] = of the bg terms.  PnGeomRay is the one statement of both passes.
+struct PnGeomRay {
+    float inv, d, ed, eb, m, w;           // 1 / (acc + 1e-6), depth, m (d - gt), (1 - m) (T - 1), m, 1 - m
+    __device__ __forceinline__ PnGeomRay(bool hit, float depth_sum, float acc, float T, float gt, float mask) {
+        inv = 1.f / (acc + 1e-6f);
+        d = hit ? depth_sum * inv : 0.f;
+        m = mask; w = 1.f - mask;
+        ed = m * (d - gt);
+        eb = w * ((hit ? T : 1.f) - 1.f);
+    }
+};
+__global__ __launch_bounds__(256) void k_geometry_loss_forward_rays(const float *__restrict__ depth_sum, const float *__restrict__ acc, const float *__restrict__ bg_trans,
+                                                                    const int *__restrict__ hit, const float *__restrict__ gt_depth, const float *__restrict__ gt_mask,
+                                                                    int R, float *__restrict__ partial) {
+    __shared__ float red[2][4];
+    float sd = 0.f, sb = 0.f;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < R; r += gridDim.x * 256) {
+        const bool h = hit[r] > 0;
+        const PnGeomRay g(h, h ? depth_sum[r] : 0.f, h ? acc[r] : 0.f, h ? bg_trans[r] : 1.f, gt_depth[r], gt_mask[r]);
+        sd += g.ed * g.ed;
+        sb += g.eb * g.eb;
+    }
+    sd = pn_wave_sum(sd); sb = pn_wave_sum(sb);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sd; red[1][threadIdx.x >> 6] = sb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        partial[gridDim.x + blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
+}
+// grad_geom [R,3] = (d / d depth_sum, d / d acc, d / d T) of gscale[0] * (depth numerator) + gscale[1] * (bg numerator); zeros on a miss.
+// The 1 / (acc + 1e-6) of a hit but almost transparent ray is the reference's formula and is kept.
+__global__ __launch_bounds__(256) void k_geometry_loss_backward_rays(const float *__restrict__ depth_sum, const float *__restrict__ acc, const float *__restrict__ bg_trans,
+                                                                     const int *__restrict__ hit, const float *__restrict__ gt_depth, const float *__restrict__ gt_mask,
+                                                                     int R, const float *__restrict__ gscale, float *__restrict__ grad_geom) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    float g_ds = 0.f, g_acc = 0.f, g_T = 0.f;
+    if (hit[r] > 0) {
+        const PnGeomRay g(true, depth_sum[r], acc[r], bg_trans[r], gt_depth[r], gt_mask[r]);
+        g_ds = (2.f * gscale[0]) * (g.m * g.ed) * g.inv;                  // 2 m^2 (d - gt) / (acc + 1e-6)
+        g_acc = -g_ds * g.d;
+        g_T = (2.f * gscale[1]) * (g.w * g.eb);                           // 2 (1 - m)^2 (T - 1)
+    }
+    grad_geom[3 * r] = g_ds; grad_geom[3 * r + 1] = g_acc; grad_geom[3 * r + 2] = g_T;
+}
 }  // namespace
+extern "C" int pnerf_geometry_loss_forward_rays(const float *d_depth_sum, const float *d_acc, const float *d_bg_trans, const int32_t *d_ray_hit,
+                                                const float *d_gt_depth, const float *d_gt_mask, int R, float *d_partial, void *stream) {
+    if (!d_depth_sum || !d_acc || !d_bg_trans || !d_ray_hit || !d_gt_depth || !d_gt_mask || !d_partial || R < 0) return PNERF_E_INVAL;
+    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_geometry_loss_forward_rays, dim3(pnerf_color_loss_blocks(R)), dim3(256), 0, (hipStream_t)stream, d_depth_sum, d_acc, d_bg_trans, d_ray_hit,
+                       d_gt_depth, d_gt_mask, R, d_partial);
+    PN_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int pnerf_geometry_loss_backward_rays(const float *d_depth_sum, const float *d_acc, const float *d_bg_trans, const int32_t *d_ray_hit,
+                                                 const float *d_gt_depth, const float *d_gt_mask, int R, const float *d_gscale2, float *d_grad_geom, void *stream) {
+    if (R == 0) return 0;
+    if (!d_depth_sum || !d_acc || !d_bg_trans || !d_ray_hit || !d_gt_depth || !d_gt_mask || !d_gscale2 || !d_grad_geom || R < 0) return PNERF_E_INVAL;
+    PnProfScope prof(PNK_GATHER, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_geometry_loss_backward_rays, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_depth_sum, d_acc, d_bg_trans, d_ray_hit,
+                       d_gt_depth, d_gt_mask, R, d_gscale2, d_grad_geom);
+    PN_CHECK_LAUNCH();
+    return 0;
+}
 extern "C" int pnerf_color_loss_blocks(int R) {
     const int b = (R + 255) / 256;
     return b < 1 ? 1 : (b > 1024 ? 1024 : b);

@@ -22,6 +22,14 @@ struct RmArgs {
     const unsigned char *valid8;
     int R, SR;
 };
+// the GEOM instance of k_raymarch_backward: per-ray gradients of depth_sum, acc and the background transmittance, and the
+// slots' depths when the caller supplies them (the stand-alone form; NULL: pn_pers_z of the sample positions)
+struct RmGeomArgs : RmArgs {
+    const float *grad_geom;           // [R,3] = (g_ds, g_acc, g_T)
+    const float *z;                   // [R,SR] or NULL
+};
+template <bool GEOM> struct RmArgsOf { using T = RmArgs; };
+template <> struct RmArgsOf<true> { using T = RmGeomArgs; };
 
 // Per-sample quantities of one 64-sample chunk of a ray.  `cm_prev` is the running cummax before the
 // chunk.  Returns delta (ray_dist), valid flag, and updates cm_prev.
@@ -91,13 +99,29 @@ __global__ __launch_bounds__(TPB) void k_raymarch_forward(RmArgs a, float *__res
 // order of the wave scans (a tree per lane, whose roundings neighbouring lanes do not share) costs nothing: measured per ray against float64,
 // d sigma and d rgb are as close as the fp32 autograd of the same formula or closer where the device's expf is not what limits them
 // (tests/raymarch_case.py; figures in DESIGN.md 4.9).
+// GEOM: the ray's depth_sum = sum_s bw_s z_s, acc = sum_s bw_s and background transmittance T_end are further channels of
+// the same recurrence -- with their per-ray gradients (g_ds, g_acc, g_T),  c_s += g_ds z_s + g_acc  and  S_bg += g_T  -- one fused
+// multiply-add per slot and one per ray, in double like c and S themselves; d rgb has no new term.  z_s is the perspective depth of the
+// sample (or the caller's array), 0 on a slot that is not valid: an empty slot's position is not read, and its op is 0.  With all three
+// gradients zero the additions are exact and the outputs are the GEOM = false instance's.
 constexpr int RM_BWD_MAX_SR = 64 * 64;
-__global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float *__restrict__ grad_color, float *__restrict__ grad_decoded) {
+template <bool GEOM> __device__ __forceinline__ double geom_channel(const typename RmArgsOf<GEOM>::T &a, long long slot, bool valid, double c, double g_ds, double g_acc) {
+    if constexpr (GEOM) {
+        const float z = !valid ? 0.f : (a.z ? a.z[slot] : pn_pers_z(a.cam, a.sample_loc + slot * 3));
+        return c + (g_ds * (double)z + g_acc);
+    } else {
+        return c;
+    }
+}
+template <bool GEOM>
+__global__ __launch_bounds__(TPB) void k_raymarch_backward(typename RmArgsOf<GEOM>::T a, const float *__restrict__ grad_color, float *__restrict__ grad_decoded) {
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
     if (r >= a.R) return;
     const int SR = a.SR;
     const float g0 = grad_color[3 * r], g1 = grad_color[3 * r + 1], g2 = grad_color[3 * r + 2];
+    double g_ds = 0., g_acc = 0., g_T = 0.;
+    if constexpr (GEOM) { g_ds = a.grad_geom[3 * r]; g_acc = a.grad_geom[3 * r + 1]; g_T = a.grad_geom[3 * r + 2]; }
     // pass 1: in lane i the map of chunk i >= 1, S behind the chunk -> S in front of it (nothing lies in front of chunk 0: its map is not needed)
     float cm_prev = -INFINITY;
     double ca = 1., cb = 0.;
@@ -111,6 +135,7 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
         if (s < SR) {
             const float4 f = *reinterpret_cast<const float4 *>(a.decoded + ((long long)r * SR + s) * 4);
             sigma = valid ? f.x : 0.f; c = (double)g0 * f.y + (double)g1 * f.z + (double)g2 * f.w;
+            c = geom_channel<GEOM>(a, (long long)r * SR + s, valid, c, g_ds, g_acc);
         }
         const float op = 1.f - expf(-sigma * delta);
         double ma = PnTransmittance::u_of(op, s < SR), mb = op * c;       // a lane outside the ray: u = 1, op c = 0
@@ -119,7 +144,8 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
         if (lane == (base >> 6)) { ca = ma; cb = mb; }
     }
     // lane i: S BEHIND chunk i -- the background behind the last chunk, then chunk by chunk towards the front
-    const double S_bg = a.cam.has_bg ? (double)g0 * a.cam.bg[0] + (double)g1 * a.cam.bg[1] + (double)g2 * a.cam.bg[2] : 0.;
+    double S_bg = a.cam.has_bg ? (double)g0 * a.cam.bg[0] + (double)g1 * a.cam.bg[1] + (double)g2 * a.cam.bg[2] : 0.;
+    if constexpr (GEOM) S_bg += g_T;                                      // T_end multiplies the background colour: its gradient joins g . bg
     double behind = S_bg, S_front = S_bg;
     for (int i = (SR - 1) >> 6; i >= 1; --i) {
         S_front = __shfl(ca, i, 64) * S_front + __shfl(cb, i, 64);        // in front of chunk i = behind chunk i - 1
@@ -137,6 +163,7 @@ __global__ __launch_bounds__(TPB) void k_raymarch_backward(RmArgs a, const float
         if (s < SR) {
             const float4 f = *reinterpret_cast<const float4 *>(a.decoded + ((long long)r * SR + s) * 4);
             sigma = valid ? f.x : 0.f; c = (double)g0 * f.y + (double)g1 * f.z + (double)g2 * f.w;
+            c = geom_channel<GEOM>(a, (long long)r * SR + s, valid, c, g_ds, g_acc);
         }
         const float e = expf(-sigma * delta);
         const float op = 1.f - e;
@@ -410,10 +437,24 @@ extern "C" int pnerf_render_forward_cut(const pnerf_camera *cam, const pnerf_poi
     return raymarch_launch(cam, st, d_decoded, d_ray_color, d_opacity, d_bg_trans, d_blend_w, s);
 }
 
-extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
-                                     const float *d_decoded, const float *d_weight, const float *d_grad_ray_color,
-                                     void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
-                                     void *d_ws, size_t ws_bytes, void *stream) {
+// the ray-march backward in its two instances: the existing one, or GEOM when the caller has per-ray geometry gradients
+static void raymarch_backward_launch(const RmArgs &ra, const float *d_grad_ray_color, const float *d_grad_geom, const float *d_z, float *d_grad_decoded, hipStream_t s) {
+    const dim3 grid(pn_cdiv(ra.R, TPB / 64));
+    if (!d_grad_geom) {
+        hipLaunchKernelGGL(k_raymarch_backward<false>, grid, dim3(TPB), 0, s, ra, d_grad_ray_color, d_grad_decoded);
+        return;
+    }
+    RmGeomArgs ga;
+    static_cast<RmArgs &>(ga) = ra;
+    ga.grad_geom = d_grad_geom; ga.z = d_z;
+    hipLaunchKernelGGL(k_raymarch_backward<true>, grid, dim3(TPB), 0, s, ga, d_grad_ray_color, d_grad_decoded);
+}
+
+// both forms of the fused backward; d_grad_geom == NULL: the existing route and the existing instance
+static int render_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
+                           const float *d_decoded, const float *d_weight, const float *d_grad_ray_color, const float *d_grad_geom,
+                           void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
+                           void *d_ws, size_t ws_bytes, void *stream) {
     int rc = check_step(cam, pts, st, ST_RENDER | ST_SAVING, d_decoded && d_weight && d_grad_ray_color && d_saved && d_grad_params && pg && d_ws);
     if (rc) return rc;
     const int R = st->R, SR = st->SR;
@@ -425,11 +466,22 @@ extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points
     float *grad_decoded = (float *)d_ws;
     float *partials = (float *)((char *)d_ws + gd_bytes);
     { PnProfScope prof(PNK_RAYMARCH_BWD, s);
-    hipLaunchKernelGGL(k_raymarch_backward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, rm_args(*cam, st->sample_loc, st->sample_nn, d_decoded, R, SR),
-                       d_grad_ray_color, grad_decoded); }
+    raymarch_backward_launch(rm_args(*cam, st->sample_loc, st->sample_nn, d_decoded, R, SR), d_grad_ray_color, d_grad_geom, /*z=*/nullptr, grad_decoded, s); }
     PN_CHECK_LAUNCH();
     return pn_agg_backward_launch(cam, pts, *st, d_decoded, d_weight, grad_decoded, pn_saved_carve(d_saved, st->n_valid_max, st->K), d_grad_params, pg,
                                   partials, /*x0_saved=*/false, s);
+}
+extern "C" int pnerf_render_backward(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
+                                     const float *d_decoded, const float *d_weight, const float *d_grad_ray_color,
+                                     void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
+                                     void *d_ws, size_t ws_bytes, void *stream) {
+    return render_backward(cam, pts, st, d_decoded, d_weight, d_grad_ray_color, nullptr, d_saved, d_grad_params, pg, d_ws, ws_bytes, stream);
+}
+extern "C" int pnerf_render_backward_geom(const pnerf_camera *cam, const pnerf_points *pts, const pnerf_step *st,
+                                          const float *d_decoded, const float *d_weight, const float *d_grad_ray_color, const float *d_grad_geom,
+                                          void *d_saved, float *d_grad_params, const pnerf_point_grads *pg,
+                                          void *d_ws, size_t ws_bytes, void *stream) {
+    return render_backward(cam, pts, st, d_decoded, d_weight, d_grad_ray_color, d_grad_geom, d_saved, d_grad_params, pg, d_ws, ws_bytes, stream);
 }
 
 extern "C" size_t pnerf_render_backward_workspace_bytes(int R, int SR) {
@@ -491,7 +543,20 @@ extern "C" int pnerf_raymarch_backward(const float *d_ray_dist, const uint8_t *d
     const RmArgs ra = rm_args(d_ray_dist, d_ray_valid, bg3_host, d_features, R, SR);
     hipStream_t s = (hipStream_t)stream;
     PnProfScope prof(PNK_RAYMARCH_BWD, s);
-    hipLaunchKernelGGL(k_raymarch_backward, dim3(pn_cdiv(R, TPB / 64)), dim3(TPB), 0, s, ra, d_grad_ray_color, d_grad_features);
+    raymarch_backward_launch(ra, d_grad_ray_color, nullptr, nullptr, d_grad_features, s);
+    PN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pnerf_raymarch_backward_geom(const float *d_ray_dist, const uint8_t *d_ray_valid, const float *d_features, const float *d_z, const float *bg3_host,
+                                            int R, int SR, const float *d_grad_ray_color, const float *d_grad_geom, float *d_grad_features, void *stream) {
+    if (!d_ray_dist || !d_ray_valid || !d_features || !d_z || !d_grad_ray_color || !d_grad_geom || !d_grad_features || R < 0 || SR <= 0) return PNERF_E_INVAL;
+    if (SR > RM_BWD_MAX_SR) return PNERF_E_UNSUP;
+    if (R == 0) return 0;
+    const RmArgs ra = rm_args(d_ray_dist, d_ray_valid, bg3_host, d_features, R, SR);
+    hipStream_t s = (hipStream_t)stream;
+    PnProfScope prof(PNK_RAYMARCH_BWD, s);
+    raymarch_backward_launch(ra, d_grad_ray_color, d_grad_geom, d_z, d_grad_features, s);
     PN_CHECK_LAUNCH();
     return 0;
 }

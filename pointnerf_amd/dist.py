@@ -75,6 +75,9 @@ def hot_path_loss(opt, out, gt_image, zero_epsilon=1e-3):
     """The lego script's training loss (models/base_rendering_model.py:543-551 ``ray_masked_coarse_raycolor`` x 1.0
     + 1e-6, and :630-641 ``zero_one`` on ``conf_coefficient`` x opt.zero_one_loss_weights[0]) with both means taken
     over the GLOBAL batch."""
+    if getattr(opt, "depth_loss_items", None) or getattr(opt, "bg_loss_items", None):
+        raise NotImplementedError("dist.hot_path_loss forms the colour and zero-one terms only: depth_loss_items / bg_loss_items (geometry_grad) go "
+                                  "through MvsPointsVolumetricModel.compute_losses")
     color, n_color = losses.masked_color(out, gt_image)
     zo = losses.zero_one(out, gt_image, zero_epsilon) if "conf_coefficient" in opt.zero_one_loss_items else None
     n = global_counts(n_color, 0 if zo is None else zo[1], device=color.device)          # ONE collective for both denominators

@@ -32,7 +32,8 @@ class MLPState:
 class FusedRender(torch.autograd.Function):
     """apply(env, emb, conf, dir, color[, xyz], *mlp_params) -> (ray_color [R,3], opacity [R,SR], bg_trans [R],
     blend_w [R,SR], decoded [R,SR,4], weight [R,SR,K]); only ray_color carries gradient.  ``xyz`` (the point positions, the tensor
-    ``env['xyz']`` is a flat view of) is passed only when ``env['xyz_grad']``: it then receives d xyz.
+    ``env['xyz']`` is a flat view of) is passed only when ``env['xyz_grad']``: it then receives d xyz.  With ``env['geometry_grad']`` the node
+    has two more outputs, depth_sum [R] and acc [R], and these and bg_trans carry gradient too.
 
     ``mlp_params`` are the aggregator's nn.Parameters in ``pnerf_mlp_layout`` order; they are views of the flat
     vector ``env['flat']`` the kernels read, and are passed only so that autograd (and DDP-style hooks) see them:
@@ -92,13 +93,29 @@ class FusedRender(torch.autograd.Function):
         if zo_sum is None:
             zo_sum = torch.zeros((), dtype=torch.float32, device=fwd["ray_color"].device)
             nondiff.append(zo_sum)
+        # env["geometry_grad"]: the ray's depth_sum, acc and background transmittance are differentiable outputs of this node
+        # -- an eighth and a ninth output from one ops.ray_geometry launch on the tensors the render left on the device, and bg_trans no
+        # longer marked -- whose gradients the backward hands to the ray march as further channels (pnerf_render_backward_geom)
+        ctx.geom = bool(env.get("geometry_grad"))
+        if ctx.geom:
+            dense = env["dense"]
+            geo = ops.ray_geometry(env["cam"], dense["sample_loc"], dense["sample_nn"], dense["ray_hit"], fwd["opacity"], fwd["blend_w"])
+            nondiff =[t for t in nondiff if t is not fwd["bg_trans"]]
+            ctx.mark_non_differentiable(*nondiff)
+            return fwd["ray_color"], fwd["opacity"], fwd["bg_trans"], fwd["blend_w"], fwd["decoded"], fwd["weight"], zo_sum, geo["depth_sum"], geo["acc"]
         ctx.mark_non_differentiable(*nondiff)
         return fwd["ray_color"], fwd["opacity"], fwd["bg_trans"], fwd["blend_w"], fwd["decoded"], fwd["weight"], zo_sum
 
     @staticmethod
     def backward(ctx, g_color, *unused):
         env, fwd = ctx.env, ctx.fwd
-        g_zo = unused[-1] if (ctx.zo is not None and unused) else None         # gradient of the seventh output (the zero-one numerator)
+        g_zo = unused[5] if (ctx.zo is not None and len(unused) > 5) else None # gradient of the seventh output (the zero-one numerator)
+        grad_geom = None
+        if ctx.geom:                                                           # (depth_sum, acc, bg_trans): a gradient that is None counts as zeros
+            cols = (unused[6], unused[7], unused[1])
+            if any(c is not None for c in cols):
+                zero = torch.zeros(env["R"], dtype=torch.float32, device=env["raydir"].device)
+                grad_geom = torch.stack([zero if c is None else c.detach().reshape(-1).float() for c in cols], dim=1).contiguous()
         if g_color is None:
             g_color = torch.zeros(env["R"], 3, dtype=torch.float32, device=env["raydir"].device)
         if not env["train"] or (fwd["saved"] is None and not ctx.recompute):
@@ -128,10 +145,10 @@ class FusedRender(torch.autograd.Function):
             ev.record()                           # creates the hipEvent_t; re-recorded by the library between dgrad and wgrad
         zo = None if g_zo is None else (g_zo.detach().reshape(1).to(torch.float32).contiguous(), ctx.zo)
         if env["n_valid"] > 0 and ctx.recompute:
-            FusedRender._backward_in_chunks(env, ctx.pts, g_color.contiguous().float(), gflat, grads, ev)
+            FusedRender._backward_in_chunks(env, ctx.pts, g_color.contiguous().float(), gflat, grads, ev, grad_geom)
         elif env["n_valid"] > 0:
             ops.render_backward(env["cam"], ctx.pts, env["packed"], env["flat"], env["raydir"], env["dense"], env["R"],
-                                env["SR"], env["K"], env["n_valid"], fwd, g_color, gflat, grads, ready_event=ev, zero_one=zo)
+                                env["SR"], env["K"], env["n_valid"], fwd, g_color, gflat, grads, ready_event=ev, zero_one=zo, grad_geom=grad_geom)
             zo = None
         if zo is not None:
             # (no valid sample at all, or the chunk-by-chunk recompute whose chunks carry their own counters: the regulariser's own pass)
@@ -153,10 +170,11 @@ class FusedRender(torch.autograd.Function):
         return (None, grads["points_embeding"], grads["points_conf"], grads["points_dir"], grads["points_color"]) + gx + gm
 
 
-def _backward_in_chunks(env, pts, g_color, gflat, grads, ev):
+def _backward_in_chunks(env, pts, g_color, gflat, grads, ev, grad_geom=None):
     """Backward of a render step whose saved activations do not fit the arena budget: for consecutive runs of rays, re-run the
     training forward (its saved activations within the budget) and the backward; gradients accumulate in the same buffers.
-    One host synchronisation per chunk (its number of valid samples sizes its arena)."""
+    One host synchronisation per chunk (its number of valid samples sizes its arena).  ``grad_geom`` [R,3] (geometry_grad) is sliced per
+    chunk like ``g_color``."""
     lib = L.lib()
     dense, R, SR, K = env["dense"], env["R"], env["SR"], env["K"]
     budget = ops.arena_budget_bytes()
@@ -183,7 +201,7 @@ def _backward_in_chunks(env, pts, g_color, gflat, grads, ev):
         # the chunk that is processed LAST (every earlier chunk's atomics must be behind it)
         handed = ev is not None and not todo
         ops.render_backward(env["cam"], pts, env["packed"], env["flat"], rd, sub, r1 - r0, SR, K, n_c, f, g_color[r0:r1], gflat, grads,
-                            ready_event=ev if handed else None)
+                            ready_event=ev if handed else None, grad_geom=None if grad_geom is None else grad_geom[r0:r1])
         ops.ARENA.give(f["saved"])
     if ev is not None and not handed:
         # the trailing run(s) of rays had no valid sample (or nothing was processed at all): the event still carries its record from

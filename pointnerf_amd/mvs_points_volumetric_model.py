@@ -110,8 +110,13 @@ class MvsPointsVolumetricModel:
             items = _as_list(getattr(opt, what + "_loss_items", None))
             setattr(opt, what + "_loss_items", items)
             setattr(opt, what + "_loss_weights", _broadcast_weights(getattr(opt, what + "_loss_weights", [1.0]), items, what))
-        if opt.depth_loss_items or opt.bg_loss_items:
-            raise NotImplementedError("depth / bg losses need compute_depth and gt masks, which no point-nerf script enables")
+        # depth and mask supervision (base_rendering_model.py:610-626) on the renderer's differentiable geometry (net_ray_marching.geometry_grad,
+        # set in create_network_models): the one item of each kind the renderer hands out
+        for what, served in (("depth", "coarse_depth"), ("bg", "coarse_is_background")):
+            for name in getattr(opt, what + "_loss_items"):
+                if name != served:
+                    raise NotImplementedError("%s_loss_items: %r is not built (only %r, on the renderer's differentiable geometry)" % (what, name, served))
+        self.loss_names += opt.depth_loss_items + opt.bg_loss_items
         self.loss_names += opt.zero_one_loss_items
         if opt.sparse_loss_weight > 0:
             self.loss_names += ["sparse"]
@@ -140,9 +145,11 @@ class MvsPointsVolumetricModel:
         self.net_ray_marching = NeuralPointsRayMarching(aggregator=self.aggregator, neural_points=self.neural_points, opt=opt,
                                                         num_pos_freqs=getattr(opt, "num_pos_freqs", 0),
                                                         num_viewdir_freqs=getattr(opt, "num_viewdir_freqs", 0)).to(self.device)
+        if opt.depth_loss_items or opt.bg_loss_items:
+            self.net_ray_marching.geometry_grad = True       # compute_losses reads "_dense_geometry" (losses.depth / losses.background)
         if self.device.type == "cuda":
             self.aggregator.flatten_()
-            self.net_ray_marching.fused_zero_one = True      # compute_losses takes the fused zero-one forms (losses.zero_one)
+            self.net_ray_marching.fused_zero_one = True     # compute_losses takes the fused zero-one forms (losses.zero_one)
             # the colour loss over the renderer's DENSE ray colours (ops.ColorLossRays; no compaction of the hit rays, no scatter back): taken when
             # every colour-loss item that carries a gradient is a ray_masked one -- the lego script's items are (ray_masked 1.0, ray_miss 0.0,
             # full image 0.0); ray_miss predicts the constant background and has no gradient, a full-image item with a non-zero weight would
@@ -318,6 +325,15 @@ class MvsPointsVolumetricModel:
                 loss = ((pred - gt) ** 2).sum() / pdist.at_least_one(n)
             self.loss_total = self.loss_total + (loss * opt.color_loss_weights[i] + 1e-6 / W)
             setattr(self, "loss_" + name, loss)
+        for what, items, weights in (("depth", opt.depth_loss_items, opt.depth_loss_weights), ("bg", opt.bg_loss_items, opt.bg_loss_weights)):
+            for i, name in enumerate(items):
+                for key, t in (("gt_depth", self.gt_depth), ("gt_mask", self.gt_mask)):
+                    if t is None and (key == "gt_mask" or what == "depth"):
+                        raise RuntimeError("%s_loss_items %r needs %r in the input (set_input found none)" % (what, name, key))
+                s, count = losses.depth(out, self.gt_depth, self.gt_mask) if what == "depth" else losses.background(out, self.gt_mask)
+                loss = s / pdist.at_least_one(pdist.global_counts(count, device=dev)[0])
+                self.loss_total = self.loss_total + loss * weights[i]
+                setattr(self, "loss_" + name, loss)
         for i, name in enumerate(opt.zero_one_loss_items):
             term = losses.zero_one(out, self.gt_image, opt.zero_epsilon, name)       # (the three forms of conf_coefficient; any other name: the tensor)
             if term is None:

@@ -105,8 +105,16 @@ class NeuralPointsRayMarching(nn.Module):
         # the dense tensors the render left on the device.  False (default): nothing is launched and the output dict is what it was.
         # ``opt.ray_geometry`` is the initial value.
         self.ray_geometry = bool(getattr(opt, "ray_geometry", False)) if opt is not None else False
+        # Depth and mask supervision (ours): when true the render node hands out the ray's depth_sum = sum_s bw_s z_s, acc =
+        # sum_s bw_s and background transmittance as DIFFERENTIABLE outputs (one ops.ray_geometry launch on the tensors the render left on the
+        # device; the ray march's backward takes their gradients as further channels, pnerf_render_backward_geom) and ``forward`` passes them
+        # to the loss under "_dense_geometry" = (depth_sum, acc, bg_trans, hit flags), dense over the R rays, next to "_dense_color"
+        # (losses.depth / losses.background).  Distinct from ``ray_geometry`` (the maps of a render-only pass, still refused under
+        # gradients).  False (default): the node has the outputs it had and nothing is launched.  ``opt.geometry_grad`` is the initial value.
+        self.geometry_grad = bool(getattr(opt, "geometry_grad", False)) if opt is not None else False
         self.last_stats = None
         self._last_camera = None
+        self._last_geometry = None
         self._pool_rays = 0
         self._pinned_words = None
 
@@ -143,6 +151,22 @@ class NeuralPointsRayMarching(nn.Module):
                                       "-- set ray_geometry back to False for the probe pass")
         return True
 
+    def _geometry_grad_setting(self):
+        """whether this render hands out the differentiable geometry (``geometry_grad``); refuses the render-only options it has no meaning with"""
+        if not self.geometry_grad:
+            return False
+        if self.transmittance_cutoff:
+            raise NotImplementedError("geometry_grad with transmittance_cutoff = %g: the cut render is render-only and leaves the samples behind the "
+                                      "cut unshaded -- set transmittance_cutoff back to 0" % float(self.transmittance_cutoff))
+        npnt = self.neural_points
+        if isinstance(npnt.Rw2c, torch.Tensor) and npnt.Rw2c.dim() == 3:
+            raise NotImplementedError("geometry_grad with one Rw2c frame per point (a composed scene): per-point frames are render-only -- set "
+                                      "geometry_grad back to False")
+        if getattr(self.opt, "prob", 0) == 1 or bool(getattr(self, "fused_probe", False)):
+            raise NotImplementedError("geometry_grad with the probe outputs (opt.prob == 1 / fused_probe): the probe pass has its own output form "
+                                      "-- set geometry_grad back to False for the probe pass")
+        return True
+
     def render_dense(self, campos, raydir, camrotc2w, near, far, bg_color=None, train=None, zero_one_eps=None):
         """The fused step on all R rays.  Returns (ray_color [R,3], opacity, bg_trans, blend_w, decoded, weight, zo_sum, dense); zo_sum =
         the zero-one regulariser's numerator over the hit rays' conf_coefficient when a training step is given ``zero_one_eps`` (the
@@ -152,6 +176,7 @@ class NeuralPointsRayMarching(nn.Module):
         render's value), and ``last_stats`` carries ``n_shaded_samples`` / ``rays_cut``."""
         opt, npnt, agg = self.opt, self.neural_points, self.aggregator
         train = torch.is_grad_enabled() if train is None else train
+        geometry_grad = self._geometry_grad_setting()
         cut = self._cut_setting(train)
         self._geometry_setting(train)
         # xyz_grad > 0: the point positions are a leaf of the fused step (d xyz from k_agg_backward's XYZG instances)
@@ -193,7 +218,9 @@ class NeuralPointsRayMarching(nn.Module):
             env["frames"] = frames
         if cut is not None:
             env["cut"] = cut
-        leaves = (npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + ((npnt.xyz,) if xyz_leaf else ()) + tuple(mlp_params)
+        if geometry_grad:
+            env["geometry_grad"] = True
+        leaves =(npnt.points_embeding, npnt.points_conf, npnt.points_dir, npnt.points_color) + ((npnt.xyz,) if xyz_leaf else ()) + tuple(mlp_params)
         # The step's one host read (number of valid samples: sizes the activation arena; number of hit rays: shapes of the outputs).
         # Round 4: a TRAINING step whose arena already exists is enqueued BEFORE that read with the arena's capacity as the bound -- every
         # kernel takes the actual counts from the device (`counters`, the class partition's tile counts), the host number is only "how much
@@ -228,7 +255,9 @@ class NeuralPointsRayMarching(nn.Module):
             out = FusedRender.apply(env, *leaves)
         if cut is not None:                                   # the two counts of the cut render: on the device until somebody asks
             self.last_stats = _CutStats(self.last_stats, env["cut_counters"])
-        return out + (dense,)
+        # geometry_grad: the node's eighth and ninth output (depth_sum, acc) stay behind for ``forward``; the tuple keeps its eight places
+        self._last_geometry = tuple(out[7:9]) if geometry_grad else None
+        return tuple(out[:7]) + (dense,)
 
     def _output_forms(self):
         """THE decision of one ``forward`` call, from the caller's flags and the options: (dense colours handed out?, form of the zero-one
@@ -308,6 +337,11 @@ class NeuralPointsRayMarching(nn.Module):
                                                         hit.shape[0], SR, K)
         elif getattr(opt, "prob", 0) == 1 and output["coarse_point_opacity"].shape[1] > 0:
             self._probe_outputs(output, dense, hit)
+        geometry, self._last_geometry = self._last_geometry, None     # (not kept on the module: the tensors hold the step's graph)
+        if geometry is not None:
+            # geometry_grad: dense over the R rays and differentiable, for losses.depth / losses.background (a render-only ``ray_geometry``
+            # pass below replaces it with its own maps)
+            output["_dense_geometry"] = (geometry[0], geometry[1], bg_trans, dense["ray_hit"])
         if self._geometry_setting(torch.is_grad_enabled()):
             # (the camera record render_dense has just built: the kernel reads its position and rotation only)
             geo = ops.ray_geometry(self._last_camera, dense["sample_loc"], dense["sample_nn"], dense["ray_hit"], opacity.detach(), blend_w.detach())
@@ -404,7 +438,9 @@ def fill_invalid(output, bg_color, tonemap_func=None, bg_ray=None, prob=0):
                 t[0, sel] = output[k][0]
                 out[k] = t
     dense_geometry = output.get("_dense_geometry")
-    for k, name in GEOMETRY_KEYS:              # the depth and opacity maps of a ``ray_geometry`` render: 0 on the rays that missed
+    if isinstance(dense_geometry, tuple):      # the differentiable form of a ``geometry_grad`` step: for the loss, not a set of maps
+        dense_geometry = None
+    for k, name in GEOMETRY_KEYS:             # the depth and opacity maps of a ``ray_geometry`` render: 0 on the rays that missed
         if dense_geometry is not None:         # (ops.ray_geometry has written every ray's value, zeros for the misses: the scatter's result)
             out[k] = dense_geometry[name][None, :, None]
         elif output.get(k) is not None:

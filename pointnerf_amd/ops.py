@@ -494,20 +494,27 @@ def cut_stage(cam, sample_loc, sample_nn, ray_hit, decoded, cutoff, stage_sample
     return out
 
 
-def render_backward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, fwd, grad_ray_color, grad_flat, grads, ready_event=None, zero_one=None):
+def render_backward(cam, pts, packed, flat, raydir, dense, R, SR, K, n_valid, fwd, grad_ray_color, grad_flat, grads, ready_event=None, zero_one=None,
+                    grad_geom=None):
     """pnerf_render_backward: accumulates into grad_flat (MLP) and grads = dict(points_embeding=..., points_conf=...,
     points_dir=..., points_color=...) (device tensors, same shapes as the parameters); an ``xyz`` entry ([N,3] or [1,N,3]) receives d xyz
     (xyz_grad: pnerf_point_grads.xyz), without it none is formed.  ``zero_one`` = (scale [1] f32 device tensor, eps): the
     conf gradient of the zero-one regulariser over the hit rays' neighbor table is added by the same call (pnerf_point_grads.zero_one_gscale;
-    ``dense`` must be the query's own output: its counters [1] and [3] count the empty slots)."""
+    ``dense`` must be the query's own output: its counters [1] and [3] count the empty slots).  ``grad_geom`` [R,3] f32 = the per-ray gradients
+    with respect to (depth_sum, acc, bg_trans) (geometry_grad): pnerf_render_backward_geom; None: pnerf_render_backward itself."""
     lib = L.lib()
     st = make_step(raydir, dense, flat, packed, R, SR, K, n_valid)
     pg = _point_grads(grads, ready_event, zero_one)
     nws = lib.pnerf_render_backward_workspace_bytes(R, SR)
     ws = torch.empty(nws, dtype=torch.uint8, device=raydir.device)
     g = grad_ray_color.contiguous().float()
-    L.check(lib.pnerf_render_backward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), _ptr(fwd["decoded"]), _ptr(fwd["weight"]), _ptr(g),
-                                      _ptr(fwd["saved"]), _ptr(grad_flat), ctypes.byref(pg), _ptr(ws), nws, _stream()), "pnerf_render_backward")
+    if grad_geom is None:
+        L.check(lib.pnerf_render_backward(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), _ptr(fwd["decoded"]), _ptr(fwd["weight"]), _ptr(g),
+                                          _ptr(fwd["saved"]), _ptr(grad_flat), ctypes.byref(pg), _ptr(ws), nws, _stream()), "pnerf_render_backward")
+        return
+    gg = _dense_arg(grad_geom.contiguous().float(), "grad_geom", torch.float32, 3 * R)
+    L.check(lib.pnerf_render_backward_geom(ctypes.byref(cam), ctypes.byref(pts), ctypes.byref(st), _ptr(fwd["decoded"]), _ptr(fwd["weight"]), _ptr(g), _ptr(gg),
+                                           _ptr(fwd["saved"]), _ptr(grad_flat), ctypes.byref(pg), _ptr(ws), nws, _stream()), "pnerf_render_backward_geom")
 
 
 def agg_forward(cam, pts, st, train):
@@ -651,6 +658,47 @@ class ColorLossRays(torch.autograd.Function):
 
 def color_loss_sum_rays(ray_color, gt, ray_hit):
     return ColorLossRays.apply(ray_color, gt, ray_hit.contiguous())
+
+
+class GeometryLossRays(torch.autograd.Function):
+    """(sum_r m^2 (d - gt_depth)^2, sum_r (1 - m)^2 (T - 1)^2) over the DENSE per-ray geometry of a geometry_grad render: depth_sum, acc and
+    bg_trans [R] (the differentiable outputs of the render node), the rays' hit flags, gt_depth / gt_mask [R]; m = gt_mask, d = depth_sum /
+    (acc + 1e-6), a ray that missed counts with d = 0 and T = 1 (pnerf_geometry_loss_forward_rays / _backward_rays: one pass forward, one
+    backward).  The numerators of the reference's depth and bg loss items (models/base_rendering_model.py:610-626); the caller divides by its
+    global ray count.  The backward hands (g_ds, g_acc, g_T) to the three inputs, the columns of ONE [R,3] tensor -- FusedRender.backward
+    puts them back together for pnerf_render_backward_geom."""
+
+    @staticmethod
+    def forward(ctx, depth_sum, acc, bg_trans, ray_hit, gt_depth, gt_mask):
+        _need_cuda(depth_sum, "depth_sum")
+        lib = L.lib()
+        R = int(ray_hit.numel())
+        f32 = torch.float32
+        flat = lambda t: t.detach().reshape(-1).contiguous().float()
+        a = (flat(depth_sum), flat(acc), flat(bg_trans), ray_hit.reshape(-1).contiguous(), flat(gt_depth), flat(gt_mask))
+        _dense_args("ray_hit", a[3], ("depth_sum", a[0], f32, R), ("acc", a[1], f32, R), ("bg_trans", a[2], f32, R), ("ray_hit", a[3], torch.int32, R),
+                    ("gt_depth", a[4], f32, R), ("gt_mask", a[5], f32, R))
+        nb = lib.pnerf_color_loss_blocks(R)
+        part = torch.empty(2, nb, dtype=f32, device=a[0].device)
+        L.check(lib.pnerf_geometry_loss_forward_rays(*[_ptr(t) for t in a], R, _ptr(part), _stream()), "pnerf_geometry_loss_forward_rays")
+        ctx.save_for_backward(*a)
+        ctx.shapes = (depth_sum.shape, acc.shape, bg_trans.shape)
+        sums = part.sum(dim=1)
+        return sums[0], sums[1]
+
+    @staticmethod
+    def backward(ctx, g_depth, g_bg):
+        a = ctx.saved_tensors
+        R = int(a[3].numel())
+        dev = a[0].device
+        gs = torch.stack([torch.zeros((), device=dev) if g is None else g.detach().reshape(()).to(torch.float32) for g in (g_depth, g_bg)]).contiguous()
+        grad = torch.empty(R, 3, dtype=torch.float32, device=dev)
+        L.check(L.lib().pnerf_geometry_loss_backward_rays(*[_ptr(t) for t in a], R, _ptr(gs), _ptr(grad), _stream()), "pnerf_geometry_loss_backward_rays")
+        return grad[:, 0].reshape(ctx.shapes[0]), grad[:, 1].reshape(ctx.shapes[1]), grad[:, 2].reshape(ctx.shapes[2]), None, None, None
+
+
+def geometry_loss_sums_rays(depth_sum, acc, bg_trans, ray_hit, gt_depth, gt_mask):
+    return GeometryLossRays.apply(depth_sum, acc, bg_trans, ray_hit, gt_depth, gt_mask)
 
 
 def set_inference_products(n):
