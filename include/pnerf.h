@@ -449,6 +449,48 @@ int pnerf_extract_2d(const float *d_cam_xyz, int64_t n_points, const pnerf_view_
 int pnerf_point_dirs(const float *d_cam_xyz, int64_t n_points, const float *cam_pos_cam_host, int n_views, const float *rot1_host9,
                      const float *rot2_host9, float *d_dirs, void *stream);
 
+/* ---- point initialisation: from one depth map per view to the raw cloud (run/train_ft.py:96-146), csrc/depthfuse.hip.
+ *
+ * pnerf_depth_consistency: the geometric part of filter_by_masks_gpu (models/mvs/filter_utils.py:222-259 = the loop over
+ * check_geometric_consistency_gpu :203-218 / reproject_with_depth_gpu :157-199) for ALL pairs of views in one launch.  d_depth [V,H,W] f32;
+ * view_hw_host [V,2] i32 = every view's (H, W): the reference assumes one size, a view of another size -> PNERF_E_UNSUP.  d_pairs
+ * [V,V,PNERF_DF_PAIR_FLOATS] f32, entry (r, s) for reference view r and source view s (the diagonal is not read), with
+ * E_s E_r^-1 = [R_sr t_sr], E_r E_s^-1 = [R_rs t_rs] formed in float64 and rounded once:
+ *   [0..8] K_s R_sr K_r^-1, [9..11] K_s t_sr, [12..20] K_r R_rs K_s^-1, [21..23] K_r t_rs, [24..26] row 2 of R_rs K_s^-1, [27] t_rs[2], rest 0.
+ * Per reference pixel (x, y) with d = d_depth[r,y,x] and every s != r: (X, Y, Z) = d [0..8] (x, y, 1) + [9..11]; (x_s, y_s) = (X / Z, Y / Z);
+ * d_s = the bilinear sample of view s there, coordinates clamped to the image (grid_sample align_corners, border: an out-of-image projection
+ * is not rejected by itself); (X', Y', Z') = d_s [12..20] (x_s, y_s, 1) + [21..23]; d' = d_s [24..26] (x_s, y_s, 1) + [27]; the pair passes if
+ * |(X' / Z', Y' / Z') - (x, y)| < 1 and |d' - d| / d < 0.01 (d == 0, NaN, inf fail).  d_geo_mask_sum [V,H,W] i32 = the number of passing s;
+ * d_depth_avg [V,H,W] f32 = (sum of the passing d' in ascending s + d) / (count + 1).  No atomics: two calls give the same bits.
+ * PNERF_E_INVAL: V < 1, H or W < 2, a null pointer; PNERF_E_UNSUP: views of different size, V > 65535, more than 2^31 - 257 pixels. */
+#define PNERF_DF_PAIR_FLOATS 32
+int pnerf_depth_consistency(const float *d_depth, const int32_t *view_hw_host, int V, const float *d_pairs, int32_t *d_geo_mask_sum,
+                            float *d_depth_avg, void *stream);
+/* pnerf_depth_fuse_select: the selection of filter_by_masks_gpu (models/mvs/filter_utils.py:259-291 with reassign_conf :294-297 and
+ * range_mask_torch :146-154) on the dense maps above.  A pixel is kept if d_confidence [V,H,W] > depth_conf_thresh, d_points_mask [V,H,W] u8
+ * != 0, (V > 1 only) d_geo_mask_sum >= geo_cnsst_num, and (ranges6_host != NULL) its world position lies in [ranges[0..2], ranges[3..5]].
+ * Kept pixels are written in ascending (view, row, column) -- the order of the reference's boolean indexing, view after view:
+ *   d_xyz_cam [n,3] = (d_cam_xyz[v,y,x,0], d_cam_xyz[v,y,x,1], d_depth_avg[v,y,x]) (x, y as given, not rescaled to the averaged depth),
+ *   d_xyz_world [n,3] = [xyz_cam 1] @ d_inv_ext[v]^T (d_inv_ext [V,16]: the inverse extrinsics, row-major; k ascending, no FMA),
+ *   d_conf_out [n] = the confidence, times conf_factor10_host[clamp(geo_mask_sum - geo_cnsst_num + 1, 1, 10) - 1] when that table is given
+ *   (the host's 1 - 1 / 1.14869^k, k = 1..10: reassign_conf), d_view_id [n] i32 = v; *d_count = n (device).  All outputs are sized for
+ *   V*H*W rows.  d_ws holds pnerf_depth_fuse_select_workspace_bytes(V, H, W) (0 for invalid sizes).  No atomics.
+ * PNERF_E_INVAL: V < 1, H or W < 2, a null pointer other than the two host tables; PNERF_E_WS; PNERF_E_UNSUP: more than 2^31 - 257 pixels. */
+size_t pnerf_depth_fuse_select_workspace_bytes(int V, int H, int W);
+int pnerf_depth_fuse_select(const int32_t *d_geo_mask_sum, const float *d_depth_avg, const float *d_cam_xyz, const float *d_confidence,
+                            const uint8_t *d_points_mask, const float *d_inv_ext, int V, int H, int W, float depth_conf_thresh,
+                            int geo_cnsst_num, const float *conf_factor10_host, const float *ranges6_host, float *d_xyz_cam,
+                            float *d_xyz_world, float *d_conf_out, int32_t *d_view_id, int32_t *d_count, void *d_ws, size_t ws_bytes,
+                            void *stream);
+/* pnerf_alpha_hull: the visual hull of alpha_masking (models/mvs/mvs_utils.py:573-607).  d_points [n,3] world positions, d_alphas [V,H,W] f32,
+ * d_w2c [V,16], d_intrinsics [V,9] row-major.  Per view: c = [p 1] @ w2c^T, q = c @ K^T, pixel = floor(q.xy / q.z) clamped to the image
+ * (NaN -> 0); m = alpha there, + 1 if use_range_mask != 0 and the unclamped pixel is outside the image (opt.alpha_range > 0 or
+ * opt.inall_img == 0: such a view does not carve); the view passes if m > 0.1 and (near_far2_host != NULL) near_far2_host[0] <= c.z <=
+ * near_far2_host[1] (the caller passes near - 1 and far).  d_mask [n] u8 = 1 where every view passes.
+ * PNERF_E_INVAL: V, H or W < 1, n < 0, a null pointer other than near_far2_host while n > 0.  n == 0: nothing is enqueued. */
+int pnerf_alpha_hull(const float *d_points, int64_t n_points, const float *d_alphas, const float *d_w2c, const float *d_intrinsics, int V,
+                     int H, int W, int use_range_mask, const float *near_far2_host, uint8_t *d_mask, void *stream);
+
 /* ---- evaluation scores of a rendered image against its ground truth (run/evaluate.py:55-61,76 report_metrics: compare_psnr,
  * compare_ssim(gt, img, 11, multichannel=True) and mean_squared_error over the PNGs that utils/visualizer.py:58-59 wrote).
  * d_img / d_gt [H,W,3] f32.  quantize8 != 0 first maps every pixel of both images through that PNG round trip,

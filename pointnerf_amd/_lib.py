@@ -15,8 +15,9 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1006                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1007                  # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
+DF_PAIR_FLOATS = 32                 # PNERF_DF_PAIR_FLOATS
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
 MLP_NTENSORS = 18
 
@@ -95,6 +96,16 @@ PROTOTYPES = {
     "pnerf_extract_2d": (c_int, [c_void_p, c_i64, ctypes.POINTER(ViewDesc), c_int, ctypes.POINTER(MapDesc), c_int, c_int, c_int, c_int, c_f32,
                                  c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnerf_point_dirs": (c_int, [c_void_p, c_i64, ctypes.POINTER(c_f32), c_int, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_void_p, c_void_p]),
+    # (depth, view_hw_host, V, pairs, geo_mask_sum, depth_avg, stream)
+    "pnerf_depth_consistency": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pnerf_depth_fuse_select_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    # (geo_mask_sum, depth_avg, cam_xyz, confidence, points_mask, inv_ext, V, H, W, conf_thresh, geo_cnsst_num, conf_factor10_host, ranges6_host,
+    #  xyz_cam, xyz_world, conf_out, view_id, count, ws, ws_bytes, stream)
+    "pnerf_depth_fuse_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_f32, c_int,
+                                        ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    # (points, n, alphas, w2c, intrinsics, V, H, W, use_range_mask, near_far2_host, mask, stream)
+    "pnerf_alpha_hull": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_f32), c_void_p, c_void_p]),
     "pnerf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_void_p]),
     "pnerf_adam_step_multi": (c_int, [ctypes.POINTER(AdamTensor), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
     "pnerf_mlp_layout": (c_int, [c_int, ctypes.POINTER(c_i64)]),

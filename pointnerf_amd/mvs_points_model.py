@@ -3,7 +3,8 @@ that feeds the hot path and needs no network -- ``extract_2d`` (:198-218) and ``
 signatures, argument meaning and return arity, computed by libpnerf_hip.so (csrc/embed2d.hip: projection into the source views, in-image /
 z-buffer masks of ``homo_warp_nongrid`` / ``homo_warp_nongrid_occ`` models/mvs/mvs_utils.py:299-315,333-369, bilinear ``grid_sample`` of
 ``extract_from_2d_grid`` :411-421, the per-view unit directions :239-251).  ``img_feats`` -- the source images and the feature pyramid of the
-reference's FeatureNet -- are inputs; the 2-D / MVS networks, ``gen_points`` and the depth filters stay outside the hot-path scope and raise.
+reference's FeatureNet -- are inputs; the 2-D / MVS networks and ``gen_points`` stay outside the hot-path scope and raise.  Given depth maps
+become the candidate points in ``point_init``: ``points_from_depth_maps`` / ``filter_by_masks_gpu`` / ``alpha_masking``.
 Batch size 1, like every reference script (``full_src_feat[0, mask[0,:,0], :]``, mvs_utils.py:419)."""
 import ctypes
 
@@ -47,7 +48,8 @@ class MvsPointsModel(nn.Module):
         raise NotImplementedError("FeatureNet (models/mvs/models.py) is outside the hot-path scope: pass img_feats in")
 
     def gen_points(self, batch):
-        raise NotImplementedError("MVSNet depth estimation (models/mvs/mvs_points_model.py:262-) is outside the hot-path scope")
+        raise NotImplementedError("MVSNet depth estimation (models/mvs/mvs_points_model.py:262-) is outside the hot-path scope: bring the depth "
+                                  "maps and call point_init.points_from_depth_maps (or filter_by_masks_gpu / alpha_masking)")
 
     # ---- the path ---------------------------------------------------------------------------------------------------------------------
     def extract_2d(self, img_feats, view_ids, layer_ids, intrinsics, c2ws, w2cs, cam_xyz, HD, WD, cam_vid=0, return_mask=False):

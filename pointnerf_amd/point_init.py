@@ -4,12 +4,18 @@ run/train_ft_nonstop.py:138-139) and ``construct_vox_points_xyz`` (:503-517; dat
 ``torch_scatter``: same arguments, same returns (centroids, voxel coordinates in ``torch.unique(dim=0)`` order, index of the
 member closest to each centroid), computed by libpnerf_hip.so (csrc/pointinit.hip) deterministically -- the reference's
 scatter_mean adds in atomic order, ties of scatter_min are implementation-defined; here sums run in point order and ties go to
-the lowest index.  ``partition_xyz`` (voxelise by one cloud, average another) is not used by any reference script and raises."""
+the lowest index.  ``partition_xyz`` (voxelise by one cloud, average another) is not used by any reference script and raises.
+
+In front of it, the step from one depth map per view to that raw cloud (run/train_ft.py:96-146; csrc/depthfuse.hip): ``filter_by_masks_gpu``
+(models/mvs/filter_utils.py:222-291) and ``alpha_masking`` (models/mvs/mvs_utils.py:573-607) with the reference's signatures and returns,
+``depth_consistency`` (the dense per-view maps of the filter) and ``points_from_depth_maps`` (the plain-tensor front door: depth maps in,
+points ready for ``MvsPointsModel.query_embedding`` out).  The depth maps are inputs: MVSNet, a depth sensor or this library's own
+``ray_geometry`` maps."""
 import ctypes
 
 import torch
 
-from . import _lib as L
+from . import _lib as L, ops
 
 
 def _space(xyz, vox_res, space_min, space_max):
@@ -63,3 +69,167 @@ def construct_vox_points_closest(xyz_val, vox_res, partition_xyz=None, space_min
 def construct_vox_points_xyz(xyz_val, vox_res, partition_xyz=None, space_min=None, space_max=None):
     """-> xyz_centroid [M,3]; mvs_utils.py:503-517."""
     return _downsample(xyz_val, vox_res, partition_xyz, space_min, space_max)[0]
+
+
+# ---- depth-map fusion (csrc/depthfuse.hip) ---------------------------------------------------------------------------------------------
+def _pair_tables(intrinsics, extrinsics):
+    """[V,V,DF_PAIR_FLOATS] fp32 (host): per (reference r, source s) the two reprojections with the intrinsics folded in, formed in float64
+    with batched 4 x 4 arithmetic and rounded once (include/pnerf.h, pnerf_depth_consistency)."""
+    K = intrinsics.detach().to("cpu", torch.float64).reshape(-1, 3, 3)
+    E = extrinsics.detach().to("cpu", torch.float64).reshape(-1, 4, 4)
+    V = E.shape[0]
+    Kinv, Einv = torch.linalg.inv(K), torch.linalg.inv(E)
+    fwd = E[None, :] @ Einv[:, None]                        # [r,s] = E_s E_r^-1
+    bwd = E[:, None] @ Einv[None, :]                        # [r,s] = E_r E_s^-1
+    T = torch.zeros(V, V, L.DF_PAIR_FLOATS, dtype=torch.float64)
+    T[..., 0:9] = (K[None, :] @ fwd[..., :3, :3] @ Kinv[:, None]).reshape(V, V, 9)
+    T[..., 9:12] = (K[None, :] @ fwd[..., :3, 3:4]).reshape(V, V, 3)
+    RK = bwd[..., :3, :3] @ Kinv[None, :]
+    T[..., 12:21] = (K[:, None] @ RK).reshape(V, V, 9)
+    T[..., 21:24] = (K[:, None] @ bwd[..., :3, 3:4]).reshape(V, V, 3)
+    T[..., 24:27] = RK[..., 2, :]
+    T[..., 27] = bwd[..., 2, 3]
+    return T.to(torch.float32).contiguous()
+
+
+def _same_size(shapes):
+    if any(tuple(sh) != tuple(shapes[0]) for sh in shapes):
+        L.check(-4, "depth fusion (views of different size: %s)" % sorted({tuple(sh) for sh in shapes}))
+
+
+def depth_consistency(depth, intrinsics, extrinsics):
+    """depth [V,H,W], intrinsics [V,3,3], extrinsics [V,4,4] (world to camera) -> (geo_mask_sum [V,H,W] int32: the number of other views
+    whose reprojection agrees with the pixel (< 1 pixel, < 1 % depth; filter_utils.py:203-218), depth_avg [V,H,W]: the mean of the pixel's
+    depth and the agreeing reprojected depths (:259)).  Useful alone as a per-view confidence map."""
+    ops._need_cuda(depth, "depth")
+    if depth.dim() != 3:
+        raise ValueError("pointnerf_amd: depth must be [V,H,W], got %s" % list(depth.shape))
+    dev = depth.device
+    d = depth.detach().contiguous().float()
+    V, H, W = d.shape
+    pairs = _pair_tables(intrinsics, extrinsics)
+    if pairs.shape[0] != V:
+        raise ValueError("pointnerf_amd: %d depth maps, %d cameras" % (V, pairs.shape[0]))
+    pairs = pairs.to(dev)
+    geo = torch.empty(V, H, W, dtype=torch.int32, device=dev)
+    avg = torch.empty(V, H, W, dtype=torch.float32, device=dev)
+    hw = (ctypes.c_int32 * (2 * V))(*([H, W] * V))
+    L.check(L.lib().pnerf_depth_consistency(ops._ptr(d), hw, V, ops._ptr(pairs), ops._ptr(geo), ops._ptr(avg), ops._stream()),
+            "pnerf_depth_consistency")
+    return geo, avg
+
+
+def _fuse(cam_xyz, confidence, points_mask, intrinsics, extrinsics, depth_conf_thresh, geo_cnsst_num, default_conf, ranges):
+    """cam_xyz [V,H,W,3], confidence [V,H,W], points_mask [V,H,W] -> (xyz_cam [n,3], xyz_world [n,3], confidence [n], view_id [n] int32)"""
+    dev = cam_xyz.device
+    cam = cam_xyz.detach().contiguous().float()
+    V, H, W, _ = cam.shape
+    geo, avg = depth_consistency(cam[..., 2], intrinsics, extrinsics)
+    conf = confidence.detach().to(dev).contiguous().float()
+    pmask = (points_mask.detach().to(dev) != 0).to(torch.uint8).contiguous()
+    # filter_utils.py:282 inverts the fp32 extrinsics with torch.inverse; here on the host (16 numbers per view)
+    inv_ext = torch.inverse(extrinsics.detach().to("cpu", torch.float32).reshape(V, 4, 4)).contiguous().to(dev)
+    fa = lambda vals: (ctypes.c_float * len(vals))(*vals)
+    factor = None
+    if default_conf > 1.0:                                   # reassign_conf (:294-297): torch's own ten values of the factor
+        factor = fa((1 - 1.0 / torch.pow(1.14869, torch.arange(1, 11, dtype=torch.int32))).tolist())
+    rng = None
+    if ranges is not None and ranges[0] > -99.0:             # range_mask_torch (:146-154)
+        rng = fa(torch.as_tensor(ranges, dtype=torch.float32).reshape(6).tolist())
+    lib = L.lib()
+    n = V * H * W
+    nws = lib.pnerf_depth_fuse_select_workspace_bytes(V, H, W)
+    ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+    xyz_cam = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    xyz_world = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    conf_out = torch.empty(n, dtype=torch.float32, device=dev)
+    view_id = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    L.check(lib.pnerf_depth_fuse_select(ops._ptr(geo), ops._ptr(avg), ops._ptr(cam), ops._ptr(conf), ops._ptr(pmask), ops._ptr(inv_ext), V, H, W,
+                                        float(depth_conf_thresh), int(geo_cnsst_num), factor, rng, ops._ptr(xyz_cam), ops._ptr(xyz_world),
+                                        ops._ptr(conf_out), ops._ptr(view_id), ops._ptr(count), ops._ptr(ws), nws, ops._stream()),
+            "pnerf_depth_fuse_select")
+    m = int(count.cpu())
+    return xyz_cam[:m], xyz_world[:m], conf_out[:m], view_id[:m]
+
+
+def filter_by_masks_gpu(cam_xyz_all, intrinsics_all, extrinsics_all, confidence_all, points_mask_all, opt, vis=False, return_w=False,
+                        cpu2gpu=False, near_fars_all=None):
+    """models/mvs/filter_utils.py:222-291: lists over the views of cam_xyz [1,1,C,H,W,3], intrinsics [1,3,3], extrinsics [1,4,4], confidence
+    [1,C,H,W], points_mask [1,C,H,W] -> (xyz_cam_lst, xyz_world_lst, confidence_filtered_lst), one entry per view, the kept pixels in
+    row-major order.  ``opt``: depth_conf_thresh, geo_cnsst_num, default_conf, ranges, manual_depth_view, far_plane_shift."""
+    if opt.manual_depth_view > 1:
+        raise NotImplementedError("manual_depth_view > 1 (several depth hypotheses per pixel, no geometric filter) is not on the path of "
+                                  "given depth maps")
+    if opt.far_plane_shift is not None:
+        raise NotImplementedError("far_plane_shift (background points behind the far plane) is not on the path of given depth maps")
+    V = len(cam_xyz_all)
+    if V < 1:
+        L.check(-1, "depth fusion (no views)")
+    _same_size([c.shape[-3:-1] for c in cam_xyz_all])
+    to = (lambda t: t.cuda()) if cpu2gpu else (lambda t: t)
+    H, W = cam_xyz_all[0].shape[-3:-1]
+    cam = torch.stack([to(c).reshape(-1, H, W, 3)[0] for c in cam_xyz_all])
+    ops._need_cuda(cam, "cam_xyz_all")
+    conf = torch.stack([to(c)[0, 0] for c in confidence_all])
+    pmask = torch.stack([to(c)[0, 0] for c in points_mask_all])
+    K = torch.stack([k[0] for k in intrinsics_all])
+    E = torch.stack([e[0] for e in extrinsics_all])
+    xyz_cam, xyz_world, cf, vid = _fuse(cam, conf, pmask, K, E, opt.depth_conf_thresh, opt.geo_cnsst_num, opt.default_conf, opt.ranges)
+    sizes = torch.bincount(vid.long(), minlength=V).tolist()
+    back = (lambda t: t.cpu()) if cpu2gpu else (lambda t: t)
+    return tuple([back(p) for p in torch.split(t, sizes)] for t in (xyz_cam, xyz_world, cf))
+
+
+def alpha_masking(points, alphas, intrinsics, c2ws, w2cs, near_far, opt=None):
+    """models/mvs/mvs_utils.py:573-607: points [N,3+] world positions, alphas[i][0] the [H,W] alpha of view i, intrinsics[i] [3,3], w2cs[i]
+    [4,4] (c2ws is not read, as there) -> bool [N]: the points every view sees on its foreground (and between near - 1 and far)."""
+    ops._need_cuda(points, "points")
+    dev = points.device
+    host = lambda lst, r, c: torch.stack([torch.as_tensor(a).detach().to("cpu", torch.float32).reshape(r, c) for a in lst]).contiguous()
+    V = len(alphas)
+    al = [torch.as_tensor(alphas[i][0]) for i in range(V)]
+    _same_size([a.shape for a in al])
+    H, W = al[0].shape
+    alpha = torch.stack([a.to(dev, torch.float32) for a in al]).contiguous()
+    K, M = host([intrinsics[i] for i in range(V)], 3, 3).to(dev), host([w2cs[i] for i in range(V)], 4, 4).to(dev)
+    pts = points.detach()[..., :3].reshape(-1, 3).contiguous().float()
+    n = pts.shape[0]
+    use_range = 1 if opt is not None and (opt.alpha_range > 0 or opt.inall_img == 0) else 0
+    nf = None
+    if near_far is not None:
+        nf = (ctypes.c_float * 2)(float(near_far[0] - 1.0), float(near_far[1]))
+    mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    L.check(L.lib().pnerf_alpha_hull(ops._ptr(pts), n, ops._ptr(alpha), ops._ptr(M), ops._ptr(K), V, H, W, use_range, nf, ops._ptr(mask),
+                                     ops._stream()), "pnerf_alpha_hull")
+    return mask.bool()
+
+
+def points_from_depth_maps(depth, intrinsics, extrinsics, confidence=None, mask=None, alphas=None, *, geo_cnsst_num, depth_conf_thresh,
+                           vox_res=0, ranges=None, near_far=None, default_conf=-1):
+    """run/train_ft.py:96-146 on plain tensors: depth [V,H,W], intrinsics [V,3,3], extrinsics [V,4,4] (world to camera), optional confidence
+    [V,H,W] (default 1), mask [V,H,W] (default all) and alphas [V,H,W] -> (xyz_world [M,3], confidence [M], view_id [M] int64).  Back-projects
+    the maps, keeps the pixels that ``geo_cnsst_num`` other views confirm (``filter_by_masks_gpu``), carves with the alphas
+    (``alpha_masking``) and, with ``vox_res > 0``, keeps one point per voxel (``construct_vox_points_closest``)."""
+    ops._need_cuda(depth, "depth")
+    dev = depth.device
+    d = depth.detach().float()
+    V, H, W = d.shape
+    K = intrinsics.detach().to(dev, torch.float32).reshape(V, 3, 3)
+    ys, xs = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float64), torch.arange(W, device=dev, dtype=torch.float64), indexing="ij")
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], dim=-1)                                                  # [H,W,3]
+    cam = (torch.einsum("vij,hwj->vhwi", torch.linalg.inv(K.double().cpu()).to(dev), pix) * d.double()[..., None]).float()   # K^-1 [x y 1] d, rounded once
+    cam[..., 2] = d                                                                                           # the depth map itself, bit for bit
+    conf = torch.ones_like(d) if confidence is None else confidence
+    pm = torch.ones_like(d, dtype=torch.bool) if mask is None else mask
+    _, xyz_world, cf, vid = _fuse(cam, conf, pm, K, extrinsics, depth_conf_thresh, geo_cnsst_num, default_conf, ranges)
+    vid = vid.long()
+    if alphas is not None:
+        al = torch.as_tensor(alphas).reshape(V, 1, H, W)
+        E = extrinsics.detach().to("cpu", torch.float32).reshape(V, 4, 4)
+        keep = alpha_masking(xyz_world, al, K.cpu(), None, E, near_far)
+        xyz_world, cf, vid = xyz_world[keep], cf[keep], vid[keep]
+    if vox_res > 0:
+        xyz_world, _, idx = construct_vox_points_closest(xyz_world, vox_res)
+        cf, vid = cf[idx], vid[idx]
+    return xyz_world, cf, vid
