@@ -491,6 +491,45 @@ int pnerf_depth_fuse_select(const int32_t *d_geo_mask_sum, const float *d_depth_
 int pnerf_alpha_hull(const float *d_points, int64_t n_points, const float *d_alphas, const float *d_w2c, const float *d_intrinsics, int V,
                      int H, int W, int use_range_mask, const float *near_far2_host, uint8_t *d_mask, void *stream);
 
+/* ---- point initialisation: from a cloud the user already has to per-view groups (run/train_ft.py:642-735, `--load_points 1/2/3`),
+ * csrc/cloudinit.hip.
+ *
+ * pnerf_nearest_view: nearest_view (run/train_ft.py:39-48) without its 10 000-point slices and [10000,M,3] temporaries.  d_xyz [n,3],
+ * d_campos [M,3] (camera centres), d_camdir [M,3] (centre rays) f32.  Per point p and camera (c, r): d = p - c,
+ * s = |d| / 200 + (1.1 - dot(d, r) / (|d| + 1e-6)); d_cam_ind [n] i32 = the camera of the smallest s, ties to the lowest index (torch.argmin);
+ * a NaN score never wins.  One thread per point, the cameras staged through LDS: any M.  The dot product is divided once (the reference
+ * divides the three components) and |d| / 200 is |d| * 0.005f: the result is the float64 argmin wherever the runner-up is farther than the
+ * reference's own fp32 rounding reaches (tests/cloudinit_case.py).  No atomics: two calls give the same bits.
+ * PNERF_E_INVAL: M < 1, n < 0, a null pointer while n > 0.  n == 0: nothing is enqueued. */
+int pnerf_nearest_view(const float *d_xyz, int64_t n, const float *d_campos, const float *d_camdir, int M, int32_t *d_cam_ind, void *stream);
+/* pnerf_occupancy_merge: the `load_points == 3` merge (run/train_ft.py:657-669 over construct_vox_points_ind, models/mvs/mvs_utils.py:520-534):
+ * the rows of cloud B [nb,3] whose cell holds no point of cloud A [na,3].  Cells are floor((x - space_min) / vox) per axis in fp32 (IEEE
+ * divide), A's with vox_size_a3_host (the reference's scalar edge / res, :531 after :525) and B's with vox_size_b3_host ((space_max -
+ * space_min) / res per axis, :530-531: the two can differ in the last bit); a cell outside [0, res)^3 holds no point of A, so such a row of B
+ * is kept.  d_mask [nb] u8 = 1 where kept, d_kept_xyz [nb rows allocated] = the kept rows in their original order (the order of the
+ * reference's boolean indexing), *d_count (device) = their number.  A res^3-bit map is set from A with an atomic OR (order-independent:
+ * two calls give the same bits).  d_ws holds pnerf_occupancy_merge_workspace_bytes(nb, res): 0 when nb > 2^31 - 257 or res^3 bits exceed
+ * that 32-bit addressing.  PNERF_E_INVAL: na or nb < 0, res < 1, a null pointer (d_a_xyz may be null when na == 0); PNERF_E_WS; PNERF_E_UNSUP
+ * as for the workspace.  nb == 0: *d_count = 0, nothing else is touched. */
+size_t pnerf_occupancy_merge_workspace_bytes(int64_t nb, int res);
+int pnerf_occupancy_merge(const float *d_a_xyz, int64_t na, const float *d_b_xyz, int64_t nb, const float *space_min3_host,
+                          const float *vox_size_a3_host, const float *vox_size_b3_host, int res, float *d_kept_xyz, int32_t *d_count,
+                          uint8_t *d_mask, void *d_ws, size_t ws_bytes, void *stream);
+/* pnerf_crop_ranges: the crop to opt.ranges (run/train_ft.py:675-680): the rows with ranges6_host[0..2] <= p <= ranges6_host[3..5] (NaN
+ * fails), outputs and errors as pnerf_occupancy_merge. */
+size_t pnerf_crop_ranges_workspace_bytes(int64_t n);
+int pnerf_crop_ranges(const float *d_xyz, int64_t n, const float *ranges6_host, float *d_kept_xyz, int32_t *d_count, uint8_t *d_mask, void *d_ws,
+                      size_t ws_bytes, void *stream);
+/* pnerf_group_by_view: torch.unique(cam_ind) and the per-view boolean indexing of run/train_ft.py:707-710 as one stable counting sort.
+ * d_cam_ind [n] i32 in [0, M).  d_order [n] i64 = the permutation that lists the points by ascending view, original order inside a view;
+ * d_offsets [M+1] i64: view v owns d_order[d_offsets[v] .. d_offsets[v+1]).  An entry outside [0, M) is left out: d_offsets[M] < n and the
+ * tail of d_order is -1.  No atomic decides a position (ranks inside 1024-point chunks, one scan over the [M, chunks] counts): two calls give
+ * the same bits.  d_ws holds pnerf_group_by_view_workspace_bytes(n, M): 0 when n > 2^31 - 257 or M * ceil(n / 1024) exceeds it.
+ * PNERF_E_INVAL: n < 0, M < 1, a null pointer; PNERF_E_WS; PNERF_E_UNSUP as for the workspace.  n == 0: d_offsets = 0. */
+size_t pnerf_group_by_view_workspace_bytes(int64_t n, int M);
+int pnerf_group_by_view(const int32_t *d_cam_ind, int64_t n, int M, int64_t *d_order, int64_t *d_offsets, void *d_ws, size_t ws_bytes,
+                        void *stream);
+
 /* ---- evaluation scores of a rendered image against its ground truth (run/evaluate.py:55-61,76 report_metrics: compare_psnr,
  * compare_ssim(gt, img, 11, multichannel=True) and mean_squared_error over the PNGs that utils/visualizer.py:58-59 wrote).
  * d_img / d_gt [H,W,3] f32.  quantize8 != 0 first maps every pixel of both images through that PNG round trip,

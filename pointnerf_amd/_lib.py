@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1007                  # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1008                 # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 DF_PAIR_FLOATS = 32                 # PNERF_DF_PAIR_FLOATS
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
@@ -106,6 +106,18 @@ PROTOTYPES = {
                                         c_void_p, c_size_t, c_void_p]),
     # (points, n, alphas, w2c, intrinsics, V, H, W, use_range_mask, near_far2_host, mask, stream)
     "pnerf_alpha_hull": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_f32), c_void_p, c_void_p]),
+    # (xyz, n, campos, camdir, M, cam_ind, stream)
+    "pnerf_nearest_view": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "pnerf_occupancy_merge_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    # (a_xyz, na, b_xyz, nb, space_min3_host, vox_size_a3_host, vox_size_b3_host, res, kept_xyz, count, mask, ws, ws_bytes, stream)
+    "pnerf_occupancy_merge": (c_int, [c_void_p, c_i64, c_void_p, c_i64, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnerf_crop_ranges_workspace_bytes": (c_size_t, [c_i64]),
+    # (xyz, n, ranges6_host, kept_xyz, count, mask, ws, ws_bytes, stream)
+    "pnerf_crop_ranges": (c_int, [c_void_p, c_i64, ctypes.POINTER(c_f32), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnerf_group_by_view_workspace_bytes": (c_size_t, [c_i64, c_int]),
+    # (cam_ind, n, M, order, offsets, ws, ws_bytes, stream)
+    "pnerf_group_by_view": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnerf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_void_p]),
     "pnerf_adam_step_multi": (c_int, [ctypes.POINTER(AdamTensor), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
     "pnerf_mlp_layout": (c_int, [c_int, ctypes.POINTER(c_i64)]),

@@ -10,7 +10,15 @@ In front of it, the step from one depth map per view to that raw cloud (run/trai
 (models/mvs/filter_utils.py:222-291) and ``alpha_masking`` (models/mvs/mvs_utils.py:573-607) with the reference's signatures and returns,
 ``depth_consistency`` (the dense per-view maps of the filter) and ``points_from_depth_maps`` (the plain-tensor front door: depth maps in,
 points ready for ``MvsPointsModel.query_embedding`` out).  The depth maps are inputs: MVSNet, a depth sensor or this library's own
-``ray_geometry`` maps."""
+``ray_geometry`` maps.
+
+The other route starts from a cloud the user already has (COLMAP, a sensor, or both: ``--load_points 1/2/3``, run/train_ft.py:642-735;
+csrc/cloudinit.hip): ``nearest_view`` (:39-48, the reference's signature and return; one thread per point with the camera loop inside
+instead of 10 000-point slices of [10000,M,3] temporaries), ``merge_by_occupancy`` (:657-669: the second cloud fills the holes of the first),
+``crop_to_ranges`` (:675-680), ``group_by_view`` (:708-710 as one stable permutation), ``points_from_cloud`` (the chain, with the tiered voxel
+down-sampling of :683-694 in between) and ``neural_points_from_cloud`` (the chain plus the per-view ``query_embedding`` loop of :718-732:
+what ``NeuralPoints.set_points`` takes).  Merge, crop and grouping equal the reference's lines exactly and keep its order; the nearest view
+is the float64 argmin wherever the runner-up is farther than the reference's own fp32 rounding reaches.  ``opt.resample_pnts`` raises."""
 import ctypes
 
 import torch
@@ -233,3 +241,177 @@ def points_from_depth_maps(depth, intrinsics, extrinsics, confidence=None, mask=
         xyz_world, _, idx = construct_vox_points_closest(xyz_world, vox_res)
         cf, vid = cf[idx], vid[idx]
     return xyz_world, cf, vid
+
+
+# ---- points from an external cloud (csrc/cloudinit.hip) -----------------------------------------------------------------------------
+def _cloud(t, name):
+    """[N,3] floating point on the device -> contiguous float32; anything else is refused (never reshaped or reinterpreted)"""
+    ops._need_cuda(t, name)
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("pointnerf_amd: %s must be [N,3], got %s" % (name, list(t.shape)))
+    if not t.is_floating_point():
+        raise ValueError("pointnerf_amd: %s must be a floating-point tensor, got %s" % (name, t.dtype))
+    return t.detach().float().contiguous()
+
+
+def _nearest_i32(campos, raydir, xyz):
+    pts, cp, cd = _cloud(xyz, "xyz"), _cloud(campos, "campos"), _cloud(raydir, "raydir")
+    if cp.shape != cd.shape:
+        raise ValueError("pointnerf_amd: %d camera positions, %d camera directions" % (cp.shape[0], cd.shape[0]))
+    n, M = pts.shape[0], cp.shape[0]
+    cam = torch.empty(n, dtype=torch.int32, device=pts.device)
+    L.check(L.lib().pnerf_nearest_view(ops._ptr(pts), n, ops._ptr(cp), ops._ptr(cd), M, ops._ptr(cam), ops._stream()), "pnerf_nearest_view")
+    return cam
+
+
+def nearest_view(campos, raydir, xyz, id_list=None):
+    """run/train_ft.py:39-48: campos [M,3] camera centres, raydir [M,3] centre rays, xyz [N,3] -> [N,1] int64: per point the camera with the
+    smallest |p - c| / 200 + (1.1 - cos(angle between p - c and the centre ray)), ties to the lowest index (``id_list`` is not read, as there)."""
+    return _nearest_i32(campos, raydir, xyz).long().view(-1, 1)
+
+
+def _kept_rows(src, launch, what):
+    """the shared tail of merge and crop: launch(kept, count, mask) -> (kept rows in order, bool mask)"""
+    n, dev = src.shape[0], src.device
+    kept = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    mask = torch.zeros(n, dtype=torch.uint8, device=dev)
+    L.check(launch(ops._ptr(kept), ops._ptr(count), ops._ptr(mask)), what)
+    return kept[:int(count.cpu())], mask.bool()
+
+
+def merge_by_occupancy(points_xyz, depth_xyz, filter_res=100, return_mask=False):
+    """run/train_ft.py:657-669: the rows of ``depth_xyz`` [Nb,3] that fall into no voxel which holds a point of ``points_xyz`` [Na,3]; the
+    ``filter_res``^3 voxels span the first cloud's cube (construct_vox_points_ind, mvs_utils.py:520-534, in its fp32 arithmetic), rows outside
+    it are kept.  -> kept rows in their order (and the bool mask [Nb])."""
+    a, b = _cloud(points_xyz, "points_xyz"), _cloud(depth_xyz, "depth_xyz")
+    res = int(filter_res)
+    if res < 1:
+        L.check(-1, "occupancy merge (filter_res=%d)" % res)
+    lib = L.lib()
+    nws = lib.pnerf_occupancy_merge_workspace_bytes(b.shape[0], res)
+    if nws == 0:
+        raise RuntimeError("pointnerf_amd: filter_res=%d is too fine for a 32-bit occupancy bitmap" % res)
+    if a.shape[0]:
+        xyz_min, xyz_max = torch.min(a, dim=-2)[0], torch.max(a, dim=-2)[0]                                   # mvs_utils.py:524-531
+        space_edge = torch.max(xyz_max - xyz_min) * 1.05
+        xyz_mid = (xyz_max + xyz_min) / 2
+        space_min, space_max = xyz_mid - space_edge / 2, xyz_mid + space_edge / 2
+        vox_a, vox_b = (space_edge / res).expand(3), (space_max - space_min) / res                            # A: the scalar edge; B: :530
+    else:                                                                                                     # nothing occupies anything
+        space_min, vox_a, vox_b = torch.zeros(3), torch.ones(3), torch.ones(3)
+    fa = lambda t: (ctypes.c_float * 3)(*t.float().cpu().tolist())
+    ws = torch.empty(nws, dtype=torch.uint8, device=b.device)
+    kept, mask = _kept_rows(b, lambda k, c, m: lib.pnerf_occupancy_merge(ops._ptr(a), a.shape[0], ops._ptr(b), b.shape[0], fa(space_min), fa(vox_a),
+                                                                         fa(vox_b), res, k, c, m, ops._ptr(ws), nws, ops._stream()),
+                            "pnerf_occupancy_merge")
+    return (kept, mask) if return_mask else kept
+
+
+def crop_to_ranges(xyz, ranges, return_mask=False):
+    """run/train_ft.py:675-680: the rows with ranges[:3] <= p <= ranges[3:], in order"""
+    pts = _cloud(xyz, "xyz")
+    rng = (ctypes.c_float * 6)(*torch.as_tensor(ranges, dtype=torch.float32).reshape(6).tolist())
+    lib = L.lib()
+    nws = lib.pnerf_crop_ranges_workspace_bytes(pts.shape[0])
+    if nws == 0:
+        L.check(-4, "crop (%d points)" % pts.shape[0])
+    ws = torch.empty(nws, dtype=torch.uint8, device=pts.device)
+    kept, mask = _kept_rows(pts, lambda k, c, m: lib.pnerf_crop_ranges(ops._ptr(pts), pts.shape[0], rng, k, c, m, ops._ptr(ws), nws, ops._stream()),
+                            "pnerf_crop_ranges")
+    return (kept, mask) if return_mask else kept
+
+
+def group_by_view(cam_ind, n_views):
+    """cam_ind [N] (or [N,1]) integer in [0, n_views) -> (order [N] int64: points by ascending view, original order inside a view -- a stable
+    argsort --, offsets [n_views+1] int64: view v owns order[offsets[v]:offsets[v+1]]); run/train_ft.py:708-710 in one pass."""
+    ops._need_cuda(cam_ind, "cam_ind")
+    if cam_ind.is_floating_point() or cam_ind.dtype == torch.bool:
+        raise ValueError("pointnerf_amd: cam_ind must be an integer tensor, got %s" % cam_ind.dtype)
+    cam = cam_ind.detach().reshape(-1).to(torch.int32).contiguous()
+    n, M, dev = cam.shape[0], int(n_views), cam.device
+    if M < 1:
+        L.check(-1, "grouping (n_views=%d)" % M)
+    lib = L.lib()
+    nws = lib.pnerf_group_by_view_workspace_bytes(n, M)
+    if nws == 0:
+        L.check(-4, "grouping (%d points, %d views)" % (n, M))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+    order = torch.empty(n, dtype=torch.int64, device=dev)
+    offsets = torch.empty(M + 1, dtype=torch.int64, device=dev)
+    L.check(lib.pnerf_group_by_view(ops._ptr(cam), n, M, ops._ptr(order), ops._ptr(offsets), ops._ptr(ws), nws, ops._stream()),
+            "pnerf_group_by_view")
+    if int(offsets[M].cpu()) != n:
+        raise ValueError("pointnerf_amd: cam_ind holds entries outside [0, %d)" % M)
+    return order, offsets
+
+
+def points_from_cloud(clouds, campos, camdir, *, vox_res=0, ranges=None, merge_res=0):
+    """run/train_ft.py:649-710 on plain tensors: ``clouds`` one [N,3] tensor or a list of them (COLMAP points, sensor points, ...), campos /
+    camdir [M,3] the cameras' centres and centre rays -> (xyz [N',3] grouped by view, view_ids [G] int64 ascending: the views that won a point,
+    offsets [G+1] int64: group g is xyz[offsets[g]:offsets[g+1]], cam_ind [N'] int64 in grouped order).
+    ``merge_res > 0`` with two clouds: the second keeps only what falls into no occupied voxel of the first (``load_points == 3``, :657-669);
+    ``ranges``: every cloud is cropped (:675-680; skipped when ranges[0] <= -99, as there); ``vox_res > 0``: cloud i keeps the member closest to
+    the centroid of each voxel at vox_res // 1.5**i (:683-694, ``points_xyz[sampled_pnt_idx]``); the clouds are concatenated; every point goes
+    to its nearest view (:707) and the points are listed view by view in their order (:708-710)."""
+    lst = [_cloud(c, "clouds[%d]" % i) for i, c in enumerate(clouds if isinstance(clouds, (list, tuple)) else [clouds])]
+    if not lst:
+        raise ValueError("pointnerf_amd: no cloud given")
+    if merge_res > 0:
+        if len(lst) != 2:
+            raise ValueError("pointnerf_amd: merge_res needs two clouds (points, depth points), got %d" % len(lst))
+        lst[1] = merge_by_occupancy(lst[0], lst[1], merge_res)
+    if ranges is not None and ranges[0] > -99.0:
+        lst = [crop_to_ranges(c, ranges) for c in lst]
+    if vox_res > 0:
+        if any(len(c) >= 80000000 for c in lst):
+            raise NotImplementedError("clouds of 80 million points and more (the reference strides them, :690) are not supported")
+        lst = [c[construct_vox_points_closest(c, vox_res // (1.5 ** i))[2]] if len(c) else c for i, c in enumerate(lst)]
+    xyz = torch.cat(lst, dim=0) if len(lst) > 1 else lst[0]
+    cam = _nearest_i32(campos, camdir, xyz)
+    order, offsets = group_by_view(cam, campos.shape[0])
+    won = offsets[1:] > offsets[:-1]
+    return xyz[order], torch.nonzero(won).reshape(-1), torch.cat([offsets[:1], offsets[1:][won]]), cam.long()[order]
+
+
+def campos_ray(c2ws, intrinsics, HDWD):
+    """The reference datasets' get_campos_ray (data/nerf_synth360_ft_dataset.py:318-333 over data/data_utils.py:55-69) on the host: c2ws
+    [V,4,4], intrinsics [V,3,3] or [3,3], HDWD = (height, width) -> (campos [V,3], camdir [V,3]: the unit ray through the centre pixel)."""
+    c2w = torch.as_tensor(c2ws).detach().to("cpu", torch.float32).reshape(-1, 4, 4)
+    K = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32).reshape(-1, 3, 3).expand(c2w.shape[0], 3, 3)
+    cx, cy = float(int(HDWD[1]) // 2), float(int(HDWD[0]) // 2)
+    d = torch.stack([(cx + 0.5 - K[:, 0, 2]) / K[:, 0, 0], (cy + 0.5 - K[:, 1, 2]) / K[:, 1, 1], torch.ones(c2w.shape[0])], dim=-1)
+    d = (d[:, None, :] @ c2w[:, :3, :3].transpose(1, 2))[:, 0]
+    return c2w[:, :3, 3].contiguous(), (d / (torch.norm(d, dim=-1, keepdim=True) + 1e-5)).contiguous()
+
+
+def neural_points_from_cloud(mvs_model, clouds, c2ws, intrinsics, HDWD, features_of, opt):
+    """run/train_ft.py:649-734 end to end: ``points_from_cloud`` (opt.vox_res, opt.ranges, the merge at 100 when opt.load_points == 3), then
+    per view that won points ``mvs_model.query_embedding`` on that view alone (:718-732) with ``features_of(view_id)``: the ``img_feats`` list
+    of the single view (level 0 the image [1,3,H,W], levels 1.. its feature maps) on the points' device.  c2ws [V,4,4], intrinsics [V,3,3].
+    -> (xyz [N,3], embedding [1,N,C], color [1,N,3], dir [1,N,3], conf [1,N,1]) as ``NeuralPoints.set_points`` takes them; the confidence is
+    scaled by opt.default_conf when that lies in (0, 1) (:728)."""
+    if getattr(opt, "resample_pnts", 0):
+        raise NotImplementedError("resample_pnts (run/train_ft.py:698-704: keep one point or a random subset) is not on this path; no reference "
+                                  "script sets it")
+    first = clouds[0] if isinstance(clouds, (list, tuple)) else clouds
+    ops._need_cuda(first, "clouds")
+    dev = first.device
+    campos, camdir = campos_ray(c2ws, intrinsics, HDWD)
+    xyz, view_ids, offsets, _ = points_from_cloud(clouds, campos.to(dev), camdir.to(dev), vox_res=opt.vox_res, ranges=opt.ranges,
+                                                  merge_res=100 if getattr(opt, "load_points", 1) == 3 else 0)
+    c2ws = torch.as_tensor(c2ws).detach().to(dev, torch.float32).reshape(-1, 4, 4)
+    K = torch.as_tensor(intrinsics).detach().to(dev, torch.float32).reshape(-1, 3, 3).expand(c2ws.shape[0], 3, 3)
+    outs, bounds = [], offsets.tolist()
+    for g, v in enumerate(view_ids.tolist()):
+        pts, c2w = xyz[bounds[g]:bounds[g + 1]], c2ws[v]
+        w2c = torch.inverse(c2w)                                                                              # :723
+        cam_xyz = (torch.cat([pts, torch.ones_like(pts[..., -1:])], dim=-1) @ w2c.transpose(0, 1))[..., :3]   # :726
+        emb, color, pdir, conf = mvs_model.query_embedding(HDWD, cam_xyz[None, ...], None, features_of(v), c2w[None, None, ...],
+                                                           w2c[None, None, ...], K[v][None, None, ...], 0, pointdir_w=True)
+        conf = conf * opt.default_conf if opt.default_conf > 0 and opt.default_conf < 1.0 else conf          # :728
+        outs.append((emb, color, pdir, conf))
+    if not outs:
+        z = lambda c: torch.zeros(1, 0, c, dtype=torch.float32, device=dev)
+        return xyz, z(opt.point_features_dim), z(3), z(3), z(1)
+    return (xyz,) + tuple(torch.cat(t, dim=1) for t in zip(*outs))
