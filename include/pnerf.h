@@ -530,6 +530,41 @@ size_t pnerf_group_by_view_workspace_bytes(int64_t n, int M);
 int pnerf_group_by_view(const int32_t *d_cam_ind, int64_t n, int M, int64_t *d_order, int64_t *d_offsets, void *d_ws, size_t ws_bytes,
                         void *stream);
 
+/* ---- point initialisation: from images to one depth map per view (the pretrained MVSNet of every per-scene script, manual_depth_view=1),
+ * csrc/mvsdepth.hip.  The 2-D and 3-D convolutions stay with the host framework; these are the stages between and behind them.
+ *
+ * pnerf_mvs_cost_volume: homo_warping (models/depth_estimators/module.py:36-70) for all views and the variance of mvsnet.py:110-122 in one
+ * pass, no warped volume.  d_feats [n_feat_sets, V, 32, h, w] f32 (n_feat_sets == B, or 1: every batch item reads the same maps, as
+ * gen_points' expanded images give, models/mvs/mvs_points_model.py:306); d_proj [B, V, 3, 4] f32 = rot | trans of proj[:, :3]; d_depth_values
+ * [B, D].  d_volume [B, 32, D, h, w] f32 (the layout CostRegNet.conv0 takes) = sum_v s^2 / V - (sum_v s / V)^2, v ascending, s the
+ * bilinear zero-padded sample of view v at  p = rot (x, y, 1) depth + trans,  g = (p.x / p.z) / ((w - 1) / 2) - 1 (y with h), un-normalised
+ * as F.grid_sample does: align_corners == 0 (the reference's call under torch >= 1.3): ((g + 1) size - 1) / 2; != 0: (g + 1) / 2 (size - 1).
+ * A position without a tap inside the map -- NaN, infinite, far outside: planes at or behind a source camera -- contributes exactly 0;
+ * every tap is bounds-checked after the conversion, nothing outside a map is read.  The maps are transposed to channels-last in d_ws
+ * (pnerf_mvs_cost_volume_workspace_bytes(n_feat_sets, V, h, w); 0 for invalid sizes).  fp32, no atomics: two calls give the same bits.
+ * PNERF_E_INVAL: B, V or D < 1, h or w < 2, n_feat_sets not 1 or B, a null pointer; PNERF_E_UNSUP: C != 32, B or 2 D or n_feat_sets V >
+ * 65535, more than 2^31 - 257 pixels per map; PNERF_E_WS. */
+size_t pnerf_mvs_cost_volume_workspace_bytes(int n_feat_sets, int V, int h, int w);
+int pnerf_mvs_cost_volume(const float *d_feats, int n_feat_sets, const float *d_proj, const float *d_depth_values, int B, int V, int C, int D,
+                          int h, int w, int align_corners, float *d_volume, void *d_ws, size_t ws_bytes, void *stream);
+/* pnerf_mvs_depth_regress: mvsnet.py:127-136 (F.softmax over D, depth_regression module.py:73-78 twice, F.pad (1, 2) + avg_pool3d(4) * 4 +
+ * gather) per pixel in one pass over the logits plus four re-reads.  d_cost_reg [B, D, h, w] f32 (the regulariser's logits), d_depth_values
+ * [B, D].  With p = softmax over D:  d_depth [B, h, w] = sum p depth_values;  idx = trunc(sum p d) clamped to [0, D - 1] (NaN -> 0);
+ * d_confidence [B, h, w] = p[idx - 1] + p[idx] + p[idx + 1] + p[idx + 2], zeros outside [0, D - 1];  d_prob_volume [B, D, h, w] = p when not
+ * NULL (a second pass; nothing is staged otherwise).  A NaN or +inf logit gives NaN outputs at its pixel and indexes nothing out of range.
+ * PNERF_E_INVAL: B, D, h or w < 1, a null pointer other than d_prob_volume; PNERF_E_UNSUP: B > 65535, more than 2^31 - 257 pixels. */
+int pnerf_mvs_depth_regress(const float *d_cost_reg, const float *d_depth_values, int B, int D, int h, int w, float *d_depth,
+                            float *d_confidence, float *d_prob_volume, void *stream);
+/* pnerf_depth_to_cam_points: the tail of gen_points for one view (models/mvs/mvs_points_model.py:329-337, gau_single_sampler :152-157 with
+ * manual_std_depth = 0, depth2point :171-182, ndc_2_cam models/mvs/mvs_utils.py:92-98).  d_depth_lr / d_conf_lr [h, w] f32.  Per output
+ * pixel (X, Y) of [H, W]: the source pixel of F.interpolate(mode='nearest') (min(floor(dst * ((float)in / out)), in - 1) per axis);
+ * d_confidence [H, W] = the confidence there; d = the depth there; d_mask [H, W] u8 = near <= d <= far; ndc = clamp((d - near) / (far - near),
+ * 0, 1) (the mask does not undo the clamp); z = ndc (far - near) + near; d_cam_xyz [H, W, 3] = ((X / (W - 1)) (W - 1) z, (Y / (H - 1)) (H - 1)
+ * z, z) @ inv_kt9_host, the host's row-major inverse of the transposed intrinsics.
+ * PNERF_E_INVAL: h or w < 1, H or W < 2, a null pointer; PNERF_E_UNSUP: more than (2^31 - 257) / 3 output pixels. */
+int pnerf_depth_to_cam_points(const float *d_depth_lr, const float *d_conf_lr, int h, int w, int H, int W, float near, float far,
+                              const float *inv_kt9_host, float *d_cam_xyz, float *d_confidence, uint8_t *d_mask, void *stream);
+
 /* ---- evaluation scores of a rendered image against its ground truth (run/evaluate.py:55-61,76 report_metrics: compare_psnr,
  * compare_ssim(gt, img, 11, multichannel=True) and mean_squared_error over the PNGs that utils/visualizer.py:58-59 wrote).
  * d_img / d_gt [H,W,3] f32.  quantize8 != 0 first maps every pixel of both images through that PNG round trip,

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libpnerf_hip.so")
 
 c_int, c_i64, c_f32, c_void_p, c_size_t = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-ABI_VERSION = 1008                 # the pnerf_version() of the include/pnerf.h this file mirrors
+ABI_VERSION = 1009                 # the pnerf_version() of the include/pnerf.h this file mirrors
 PNERF_MAX_K = 16
 DF_PAIR_FLOATS = 32                 # PNERF_DF_PAIR_FLOATS
 GI_N_IN_GRID, GI_N_OCC, GI_MAX_CNT, GI_CELL0, GI_FIRST_IDX, GI_LEN = 0, 1, 2, 3, 4, 8
@@ -118,6 +118,15 @@ PROTOTYPES = {
     "pnerf_group_by_view_workspace_bytes": (c_size_t, [c_i64, c_int]),
     # (cam_ind, n, M, order, offsets, ws, ws_bytes, stream)
     "pnerf_group_by_view": (c_int, [c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnerf_mvs_cost_volume_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    # (feats, n_feat_sets, proj, depth_values, B, V, C, D, h, w, align_corners, volume, ws, ws_bytes, stream)
+    "pnerf_mvs_cost_volume": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
+    # (cost_reg, depth_values, B, D, h, w, depth, confidence, prob_volume, stream)
+    "pnerf_mvs_depth_regress": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # (depth_lr, conf_lr, h, w, H, W, near, far, inv_kt9_host, cam_xyz, confidence, mask, stream)
+    "pnerf_depth_to_cam_points": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_f32, c_f32, ctypes.POINTER(c_f32), c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
     "pnerf_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, c_void_p]),
     "pnerf_adam_step_multi": (c_int, [ctypes.POINTER(AdamTensor), c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p]),
     "pnerf_mlp_layout": (c_int, [c_int, ctypes.POINTER(c_i64)]),

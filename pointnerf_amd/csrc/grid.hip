@@ -301,5 +301,5 @@ extern "C" int pnerf_points_minmax(const float *d_xyz, int64_t n, float *d_out6,
     return 0;
 }
 
-extern "C" int pnerf_version(void) { return 1008; }
+extern "C" int pnerf_version(void) { return 1009; }
 extern "C" const char *pnerf_arch(void) { return "gfx950"; }

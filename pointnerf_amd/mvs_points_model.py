@@ -3,15 +3,25 @@ that feeds the hot path and needs no network -- ``extract_2d`` (:198-218) and ``
 signatures, argument meaning and return arity, computed by libpnerf_hip.so (csrc/embed2d.hip: projection into the source views, in-image /
 z-buffer masks of ``homo_warp_nongrid`` / ``homo_warp_nongrid_occ`` models/mvs/mvs_utils.py:299-315,333-369, bilinear ``grid_sample`` of
 ``extract_from_2d_grid`` :411-421, the per-view unit directions :239-251).  ``img_feats`` -- the source images and the feature pyramid of the
-reference's FeatureNet -- are inputs; the 2-D / MVS networks and ``gen_points`` stay outside the hot-path scope and raise.  Given depth maps
-become the candidate points in ``point_init``: ``points_from_depth_maps`` / ``filter_by_masks_gpu`` / ``alpha_masking``.
+reference's FeatureNet -- are inputs of those two.
+
+A model whose ``args`` carry the reference's ``manual_depth_view`` also builds the networks (``depth_estimators``): ``get_image_features``
+(:221-222, the four-level pyramid) and ``gen_points`` (:262-341) for ``manual_depth_view == 1`` -- the pretrained MVSNet, whose cost volume
+and depth regression are csrc/mvsdepth.hip -- and ``== 0`` (given ``depths_h``); the tail of ``gen_points`` (nearest up-sampling, near / far
+mask, the clamped NDC round trip, back-projection) is one more kernel of that file.  ``load_pretrained_d_est`` (:66-74) keeps its signature.
+``manual_depth_view == -1`` or ``> 1``, ``manual_std_depth != 0`` and ``far_plane_shift`` raise, naming the option.  A model built from the
+few options ``query_embedding`` needs has no networks: its ``gen_points`` and ``get_image_features`` raise.  Given depth maps become the
+candidate points in ``point_init``: ``points_from_depth_maps`` / ``filter_by_masks_gpu`` / ``alpha_masking``.
 Batch size 1, like every reference script (``full_src_feat[0, mask[0,:,0], :]``, mvs_utils.py:419)."""
 import ctypes
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L, ops
+from .depth_estimators import MVSNet, PyramidFeatureNet
+from .point_init import depth_values_of
 
 feature_str_lst = ['appr_feature_str0', 'appr_feature_str1', 'appr_feature_str2', 'appr_feature_str3']
 
@@ -40,16 +50,80 @@ class MvsPointsModel(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
+        # the networks exist only for an ``args`` that carries the reference's ``manual_depth_view`` (:46-53: create_mvs); a model built from
+        # the few options query_embedding needs has none, and its gen_points / get_image_features raise
+        if hasattr(args, "manual_depth_view"):
+            self.FeatureNet = PyramidFeatureNet()
+            if args.manual_depth_view >= 1:
+                self.MVSNet = MVSNet(refine=False, align_corners=bool(getattr(args, "mvs_align_corners", False)))
+                if getattr(args, "pre_d_est", None) is not None:
+                    self.load_pretrained_d_est(self.MVSNet, args.pre_d_est)
         if getattr(args, "shading_feature_mlp_layer0", 0) > 0:
             self.premlp = premlp_init(args)
 
-    # ---- out of scope: the networks -------------------------------------------------------------------------------------------------
+    def load_pretrained_d_est(self, model, pre_d_est):
+        """:66-74: the checkpoint's ``model`` dictionary with ``module.`` stripped from every key, loaded strictly"""
+        print("loading model {}".format(pre_d_est))
+        state_dict = torch.load(pre_d_est, map_location=lambda storage, loc: storage)
+        model.load_state_dict(OrderedDict((k[7:], v) for k, v in state_dict["model"].items()))
+
+    # ---- the networks ---------------------------------------------------------------------------------------------------------------
     def get_image_features(self, imgs):
-        raise NotImplementedError("FeatureNet (models/mvs/models.py) is outside the hot-path scope: pass img_feats in")
+        """:221-222 -> the four-level list of models/mvs/models.py:745-756: [images [V,3,H,W], [V,8,H,W], [V,16,H/2,W/2], [V,32,H/4,W/4]]"""
+        if not hasattr(self, "FeatureNet"):
+            raise NotImplementedError("this model was built without the 2-D networks (its options carry no manual_depth_view): pass img_feats in")
+        ops._need_cuda(imgs, "imgs")
+        return self.FeatureNet(imgs[:, :self.args.init_view_num])
 
     def gen_points(self, batch):
-        raise NotImplementedError("MVSNet depth estimation (models/mvs/mvs_points_model.py:262-) is outside the hot-path scope: bring the depth "
-                                  "maps and call point_init.points_from_depth_maps (or filter_by_masks_gpu / alpha_masking)")
+        """:262-341 for ``manual_depth_view == 1`` (the pretrained MVSNet) and ``== 0`` (the batch's ``depths_h``) -> (cam_xyz_lst,
+        photometric_confidence_lst, nearfar_mask_lst, HDWD, data_mvs, intrinsics_lst, extrinsics_lst), one list entry per view of
+        ``depth_vid``: cam_xyz [1,1,1,H,W,3], confidence [1,1,H,W] (none for given depths, as there), mask [1,1,H,W]."""
+        if not hasattr(self, "FeatureNet"):
+            raise NotImplementedError("this model was built without the depth estimator (its options carry no manual_depth_view): bring the "
+                                      "depth maps and call point_init.points_from_depth_maps (or filter_by_masks_gpu / alpha_masking)")
+        args = self.args
+        mdv = args.manual_depth_view
+        if mdv == -1:
+            raise NotImplementedError("manual_depth_view == -1 (the learned probability volume, ProbNet) is not built")
+        if mdv > 1:
+            raise NotImplementedError("manual_depth_view > 1 (several depth hypotheses per pixel) is not built")
+        if getattr(args, "manual_std_depth", 0) != 0:
+            raise NotImplementedError("manual_std_depth != 0 (depths drawn around the estimate) is not built: the points would not be reproducible")
+        if getattr(args, "far_plane_shift", None) is not None:
+            raise NotImplementedError("far_plane_shift (background points behind the far plane) is not built")
+        batch.pop("scan", None)
+        ops._need_cuda(batch["images"], "batch['images']")
+        dev = batch["images"].device
+        data_mvs = {k: (v.float().to(dev) if isinstance(v, torch.Tensor) else v) for k, v in batch.items()}       # decode_batch (:126-130)
+        near_fars, intrinsics = data_mvs["near_fars"], batch["intrinsics"]
+        depth_vid = [int(c) for c in args.depth_vid]
+        cam_xyz_lst, conf_lst, mask_lst, HDWD = [], [], [], None
+        if mdv == 1:
+            nfd = ops.host_array(batch["near_fars_depth"])[0]
+            # :300-302; the reference fixes 192 planes, ``args.n_depth`` (not one of its options) overrides that
+            depth_values = depth_values_of(nfd, int(getattr(args, "n_depth", 192))).to(dev)
+            dimgs = data_mvs["mvs_images"] if "mvs_images" in data_mvs else data_mvs["images"]
+            views = dimgs[0, :args.init_view_num]
+            bproj = data_mvs["proj_mats"][0, torch.as_tensor(depth_vid, dtype=torch.long, device=dev)]          # :308
+            with torch.no_grad():
+                # :306 expands the same images once per depth view; here FeatureNet runs once per distinct image and the batch items share
+                depths, confs = self.MVSNet.depth_and_confidence(views[None].expand(len(depth_vid), -1, -1, -1, -1), bproj,
+                                                                 depth_values.expand(len(depth_vid), -1), features=self.MVSNet.features_of(views))
+            size = tuple(dimgs.shape[-2:])
+        else:
+            depths = data_mvs["depths_h"][0][depth_vid]
+            confs = torch.ones_like(depths)
+            size = tuple(depths.shape[-2:])
+        for i, vid in enumerate(depth_vid):
+            xyz, conf, mask = ops.depth_to_cam_points(depths[i], confs[i], size, near_fars[0, vid], intrinsics[0, vid])
+            cam_xyz_lst.append(xyz)
+            mask_lst.append(mask)
+            if mdv == 1:
+                conf_lst.append(conf)
+            HDWD = size
+        return (cam_xyz_lst, conf_lst, mask_lst, HDWD, data_mvs, [batch["intrinsics"][:, v, ...] for v in depth_vid],
+                [batch["w2cs"][:, v, ...] for v in depth_vid])
 
     # ---- the path ---------------------------------------------------------------------------------------------------------------------
     def extract_2d(self, img_feats, view_ids, layer_ids, intrinsics, c2ws, w2cs, cam_xyz, HD, WD, cam_vid=0, return_mask=False):

@@ -20,8 +20,10 @@ What is different in HOW:
     checkpoints interchange);
   * the masked colour loss is taken on the compact hit-ray tensor the renderer returns instead of ``masked_select``-ing it
     back out of the scattered [1,R,3] image (same elements in the same order).
-The MVSNet branch (``mode != 2``: ``net_mvs``, ``gen_points``, ``query_embedding``, ``set_bg``) is out of scope
-and raises.
+``--mode 1`` (what ``gen_points_filter_embeddings`` sets, run/train_ft.py:51-167) builds ``net_mvs`` alone -- ``MvsPointsModel`` with the
+pretrained depth estimator and the 2-D pyramid -- and serves ``setup`` / ``eval`` / ``set_input`` / ``gen_points`` (:226-230) /
+``query_embedding`` (:233-235) / ``cleanup`` and the loading of ``*_net_mvs.pth``.  ``--mode 0`` (both at once, the feed-forward training of
+the generalisable model), ``set_bg`` and ``gen_points`` on a ``--mode 2`` model raise.
 """
 import os
 
@@ -32,6 +34,7 @@ from torch.optim import lr_scheduler
 
 from . import dist as pdist
 from . import losses
+from .mvs_points_model import MvsPointsModel
 from .neural_points import NeuralPoints
 from .neural_points_volumetric_model import NeuralPointsRayMarching, fill_invalid
 from .optim import FusedAdam
@@ -76,8 +79,9 @@ class MvsPointsVolumetricModel:
 
     # ------------------------------------------------------------------ construction (base_model.py:14-25, base_rendering_model.py:361-385)
     def initialize(self, opt):
-        if getattr(opt, "mode", 2) != 2:
-            raise NotImplementedError("only --mode 2 (point-nerf only) is built; the MVSNet initialiser is out of scope")
+        self.mode = getattr(opt, "mode", 2)
+        if self.mode not in (1, 2):
+            raise NotImplementedError("--mode %r: only 2 (point-nerf only) and 1 (the MVSNet initialiser only) are built" % (self.mode,))
         self.opt = opt
         self.gpu_ids = _as_list(getattr(opt, "gpu_ids", [0]))
         self.is_train = opt.is_train
@@ -90,6 +94,14 @@ class MvsPointsVolumetricModel:
         self.top_ray_miss_ids = self.top_ray_miss_loss = None
         self.loss_total = None
         self._raw = None
+        if self.mode == 1:                                   # nothing is rendered: no loss or visual item applies
+            self.loss_names = ["total"]
+            self.net_mvs = MvsPointsModel(opt).to(self.device)      # mvs_points_volumetric_model.py:38-41
+            self.net_mvs.eval()
+            self.model_names = ["mvs"]
+            if self.is_train:
+                self.setup_optimizer(opt)
+            return
         self.check_setup_loss(opt)
         if len(self.loss_names) == 1 and opt.is_train:
             raise NotImplementedError("Requiring losses to train")
@@ -174,6 +186,8 @@ class MvsPointsVolumetricModel:
         if not self.is_train or opt.resume_dir:
             self.load_networks(opt.resume_iter)
         self.print_networks(getattr(opt, "verbose", 0))
+        if self.mode == 1:
+            return
         if opt.prob_freq > 0 and train_len is not None and opt.prob_num_step > 1:
             self.num_probe = train_len // opt.prob_num_step
             self.reset_ray_miss_ranking()
@@ -197,6 +211,13 @@ class MvsPointsVolumetricModel:
 
     # ------------------------------------------------------------------ optimizers / schedulers (mvs_points_volumetric_model.py:47-95,196-233)
     def setup_optimizer(self, opt):
+        if self.mode == 1:                                   # :60-79: one Adam over the MVS networks at mvs_lr
+            self.net_params, self.neural_params, self.mvs_params = [], [], list(self.net_mvs.parameters())
+            self.optimizer = self.neural_point_optimizer = None
+            mvs_lr = opt.mvs_lr if getattr(opt, "mvs_lr", None) is not None else opt.lr
+            self.mvs_optimizer = torch.optim.Adam(self.mvs_params, lr=mvs_lr, betas=(0.9, 0.999))
+            self.optimizers = [self.mvs_optimizer]
+            return
         named = list(self.net_ray_marching.named_parameters())
         self.net_params = [p for n, p in named if not n.startswith("neural_points")]
         self.neural_params = [p for n, p in named if n.startswith("neural_points")]
@@ -437,10 +458,23 @@ class MvsPointsVolumetricModel:
     def grow_points(self, points_xyz, points_embedding, points_color, points_dir, points_conf):
         self.neural_points.grow_points(points_xyz, points_embedding, points_color, points_dir, points_conf)
 
-    def gen_points(self, *a, **k):
-        raise NotImplementedError("MVSNet point generation is out of scope (SURVEY.md 8f f4)")
+    def gen_points(self):
+        """mvs_points_volumetric_model.py:226-230 on the input of ``set_input`` (a ``get_init_item`` dictionary) -> the ten items."""
+        if getattr(self, "net_mvs", None) is None:
+            raise NotImplementedError("gen_points needs the MVSNet initialiser: create the model with --mode 1")
+        cam_xyz_lst, photometric_confidence_lst, point_mask_lst, HDWD, data_mvs, intrinsics_lst, extrinsics_lst = self.net_mvs.gen_points(self.input)
+        return (cam_xyz_lst, photometric_confidence_lst, point_mask_lst, intrinsics_lst, extrinsics_lst, HDWD, data_mvs["c2ws"], data_mvs["w2cs"],
+                self.input["intrinsics"], self.input["near_fars"])
 
-    query_embedding = set_bg = gen_points
+    def query_embedding(self, HDWD, cam_xyz, photometric_confidence, imgs, c2ws, w2cs, intrinsics, cam_vid, pointdir_w=True):
+        """:233-235: the pyramid of ``imgs`` [1,V,3,H,W], then MvsPointsModel.query_embedding on it"""
+        if getattr(self, "net_mvs", None) is None:
+            raise NotImplementedError("query_embedding needs the MVSNet initialiser: create the model with --mode 1")
+        img_feats = self.net_mvs.get_image_features(imgs)
+        return self.net_mvs.query_embedding(HDWD, cam_xyz, photometric_confidence, img_feats, c2ws, w2cs, intrinsics, cam_vid, pointdir_w=pointdir_w)
+
+    def set_bg(self, *a, **k):
+        raise NotImplementedError("set_bg (background planes of the scannet scripts) is not built")
 
     # ------------------------------------------------------------------ reporting / checkpoints (base_model.py:66-127)
     def get_current_visuals(self, data=None):
@@ -474,6 +508,9 @@ class MvsPointsVolumetricModel:
                 continue
             sd = torch.load(path, map_location=self.device)
             dc = getattr(self.opt, "default_conf", -1.0)
+            if name == "mvs":
+                net.load_state_dict(sd, strict=False)
+                continue
             if epoch == "best" and name == "ray_marching" and 0.0 < dc <= 1.0 and self.neural_points.points_conf is not None \
                     and "neural_points.points_conf" not in sd:
                 sd["neural_points.points_conf"] = torch.ones_like(self.neural_points.points_conf) * dc
@@ -489,7 +526,7 @@ class MvsPointsVolumetricModel:
                     setattr(self.neural_points, attr, new)
                     replaced = True
             net.load_state_dict(sd, strict=False)
-        if self.device.type == "cuda":
+        if self.device.type == "cuda" and getattr(self, "aggregator", None) is not None:
             self.aggregator.flatten_()
         if self.is_train and self.optimizers and replaced:
             # new parameter objects: the optimizers are rebuilt around them, and the schedulers with them -- a scheduler left on a
@@ -502,7 +539,7 @@ class MvsPointsVolumetricModel:
     def cleanup(self):
         if getattr(self, "neural_points", None) is not None:
             self.neural_points.querier.clean_up()
-        for a in ("neural_points", "net_ray_marching", "aggregator", "output", "input", "gt_image", "_raw"):
+        for a in ("neural_points", "net_ray_marching", "net_mvs", "aggregator", "output", "input", "gt_image", "_raw"):
             setattr(self, a, None)
         self.clean_optimizer_scheduler()
 

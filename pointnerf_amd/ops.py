@@ -794,6 +794,80 @@ def image_metrics(img, gt, win=11, data_range=2.0, quantize8=True):
     return torch.stack([out4[0] / float(H * W * 3), out4[1:].sum() / float(3 * n_win)])
 
 
+# ------------------------------------------------------------------------------------------ depth maps from images (csrc/mvsdepth.hip)
+def _f32(t, name, anchor=None):
+    """a float32 contiguous device tensor (on the anchor's device) without its autograd history"""
+    _need_cuda(t, name)
+    if not t.is_floating_point():
+        raise ValueError("pointnerf_amd: %s must be a floating-point tensor, got %s" % (name, t.dtype))
+    if anchor is not None and t.device != anchor.device:
+        raise ValueError("pointnerf_amd: %s is on %s, expected %s" % (name, t.device, anchor.device))
+    return t.detach().float().contiguous()
+
+
+def mvs_cost_volume(features, proj, depth_values, align_corners=False):
+    """pnerf_mvs_cost_volume: features [V,C,h,w] (one set shared by every batch item) or [B,V,C,h,w], proj [B,V,3,4] or [B,V,4,4] (the upper
+    three rows are read, models/depth_estimators/module.py:47-48), depth_values [B,D] -> the variance volume [B,C,D,h,w] of
+    mvsnet.py:110-122.  ``align_corners=False`` is what the reference's grid_sample call does under torch >= 1.3."""
+    f = _f32(features, "features")
+    if f.dim() == 4:
+        f = f[None]
+    if f.dim() != 5:
+        raise ValueError("pointnerf_amd: features must be [V,C,h,w] or [B,V,C,h,w], got %s" % list(features.shape))
+    dv = _f32(depth_values, "depth_values", f)
+    if dv.dim() != 2:
+        raise ValueError("pointnerf_amd: depth_values must be [B,D], got %s" % list(depth_values.shape))
+    B, D = dv.shape
+    sets, V, C, h, w = f.shape
+    _need_cuda(proj, "proj")
+    if proj.dim() != 4 or proj.shape[0] != B or proj.shape[1] != V or proj.shape[2] not in (3, 4) or proj.shape[3] != 4:
+        raise ValueError("pointnerf_amd: proj must be [%d,%d,3 or 4,4], got %s" % (B, V, list(proj.shape)))
+    p = _f32(proj[:, :, :3, :], "proj", f)
+    lib = L.lib()
+    nws = lib.pnerf_mvs_cost_volume_workspace_bytes(sets, V, h, w)
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=f.device)
+    vol = torch.empty(B, C, D, h, w, dtype=torch.float32, device=f.device)
+    L.check(lib.pnerf_mvs_cost_volume(_ptr(f), sets, _ptr(p), _ptr(dv), B, V, C, D, h, w, 1 if align_corners else 0, _ptr(vol), _ptr(ws), nws,
+                                      _stream()), "pnerf_mvs_cost_volume")
+    return vol
+
+
+def mvs_depth_regress(cost_reg, depth_values, return_prob=False):
+    """pnerf_mvs_depth_regress: cost_reg [B,D,h,w] (logits), depth_values [B,D] -> (depth [B,h,w], photometric_confidence [B,h,w]) and, with
+    ``return_prob``, the softmax [B,D,h,w] (mvsnet.py:127-136)."""
+    c = _f32(cost_reg, "cost_reg")
+    dv = _f32(depth_values, "depth_values", c)
+    if c.dim() != 4 or dv.dim() != 2 or tuple(dv.shape) != tuple(c.shape[:2]):
+        raise ValueError("pointnerf_amd: cost_reg [B,D,h,w] and depth_values [B,D] expected, got %s and %s" % (list(cost_reg.shape), list(depth_values.shape)))
+    B, D, h, w = c.shape
+    depth = torch.empty(B, h, w, dtype=torch.float32, device=c.device)
+    conf = torch.empty(B, h, w, dtype=torch.float32, device=c.device)
+    prob = torch.empty(B, D, h, w, dtype=torch.float32, device=c.device) if return_prob else None
+    L.check(L.lib().pnerf_mvs_depth_regress(_ptr(c), _ptr(dv), B, D, h, w, _ptr(depth), _ptr(conf), _ptr(prob), _stream()), "pnerf_mvs_depth_regress")
+    return (depth, conf, prob) if return_prob else (depth, conf)
+
+
+def depth_to_cam_points(depth_lr, conf_lr, size, near_far, intrinsic):
+    """pnerf_depth_to_cam_points: depth_lr / conf_lr [h,w] of one view, size = (H, W), near_far = (near, far), intrinsic [3,3] -> (cam_xyz
+    [1,1,1,H,W,3], confidence [1,1,H,W], mask [1,1,H,W] bool): the tail of gen_points (models/mvs/mvs_points_model.py:329-337, 152-157,
+    171-182, mvs_utils.py:92-98).  The inverse of the transposed intrinsics is taken by the host in float32, as the reference takes it."""
+    d = _f32(depth_lr, "depth_lr")
+    c = _f32(conf_lr, "conf_lr", d)
+    if d.dim() != 2 or c.shape != d.shape:
+        raise ValueError("pointnerf_amd: depth_lr and conf_lr must be [h,w], got %s and %s" % (list(depth_lr.shape), list(conf_lr.shape)))
+    h, w = d.shape
+    H, W = int(size[0]), int(size[1])
+    K = torch.tensor(np.asarray(host_array(intrinsic) if isinstance(intrinsic, torch.Tensor) else intrinsic), dtype=torch.float32).reshape(3, 3)
+    M = (ctypes.c_float * 9)(*torch.inverse(K.t()).contiguous().reshape(-1).tolist())
+    nf = [float(v) for v in (host_array(near_far) if isinstance(near_far, torch.Tensor) else np.asarray(near_far)).reshape(-1)[:2]]
+    xyz = torch.empty(1, 1, 1, H, W, 3, dtype=torch.float32, device=d.device)
+    conf = torch.empty(1, 1, H, W, dtype=torch.float32, device=d.device)
+    mask = torch.empty(1, 1, H, W, dtype=torch.uint8, device=d.device)
+    L.check(L.lib().pnerf_depth_to_cam_points(_ptr(d), _ptr(c), h, w, H, W, nf[0], nf[1], M, _ptr(xyz), _ptr(conf), _ptr(mask), _stream()),
+            "pnerf_depth_to_cam_points")
+    return xyz, conf, mask.bool()
+
+
 # ------------------------------------------------------------------------------------------ probe pass
 PROBE_RAY_KEYS = (("ray_max_shading_opacity", 1), ("ray_max_sample_loc_w", 3), ("ray_max_far_dist", 1), ("shading_avg_color", 3),
                   ("shading_avg_dir", 3), ("shading_avg_conf", 1), ("shading_avg_embedding", 32))

@@ -9,8 +9,10 @@ the lowest index.  ``partition_xyz`` (voxelise by one cloud, average another) is
 In front of it, the step from one depth map per view to that raw cloud (run/train_ft.py:96-146; csrc/depthfuse.hip): ``filter_by_masks_gpu``
 (models/mvs/filter_utils.py:222-291) and ``alpha_masking`` (models/mvs/mvs_utils.py:573-607) with the reference's signatures and returns,
 ``depth_consistency`` (the dense per-view maps of the filter) and ``points_from_depth_maps`` (the plain-tensor front door: depth maps in,
-points ready for ``MvsPointsModel.query_embedding`` out).  The depth maps are inputs: MVSNet, a depth sensor or this library's own
-``ray_geometry`` maps.
+points ready for ``MvsPointsModel.query_embedding`` out).  The depth maps are inputs: a depth sensor, this library's own ``ray_geometry``
+maps, or ``depth_maps_from_images`` -- the pretrained MVSNet (``depth_estimators.MVSNet``; cost volume, depth regression and the tail of
+``gen_points`` in csrc/mvsdepth.hip) on plain tensors, with the relative projection matrices formed as the dataset forms them
+(``relative_proj_mats``); ``points_from_images`` is that followed by ``points_from_depth_maps``.
 
 The other route starts from a cloud the user already has (COLMAP, a sensor, or both: ``--load_points 1/2/3``, run/train_ft.py:642-735;
 csrc/cloudinit.hip): ``nearest_view`` (:39-48, the reference's signature and return; one thread per point with the camera loop inside
@@ -241,6 +243,64 @@ def points_from_depth_maps(depth, intrinsics, extrinsics, confidence=None, mask=
         xyz_world, _, idx = construct_vox_points_closest(xyz_world, vox_res)
         cf, vid = cf[idx], vid[idx]
     return xyz_world, cf, vid
+
+
+# ---- depth maps from images (csrc/mvsdepth.hip, depth_estimators.MVSNet) ------------------------------------------------------------------
+def relative_proj_mats(intrinsics, w2cs, views):
+    """The dataset's projection matrices of one init item (data/nerf_synth360_ft_dataset.py:398-400, 506-516) for the views ``views``
+    (reference first): P = [K with its first two rows / 4] [R|t] as a 4 x 4, the reference view the identity, every other P_src inv(P_ref);
+    formed in float64 on the host -> [len(views),4,4] float32."""
+    K = torch.as_tensor(intrinsics).detach().to("cpu", torch.float64).reshape(-1, 3, 3)
+    E = torch.as_tensor(w2cs).detach().to("cpu", torch.float64).reshape(-1, 4, 4)
+    P = torch.eye(4, dtype=torch.float64).repeat(len(views), 1, 1)
+    for j, v in enumerate(views):
+        Kq = K[v].clone()
+        Kq[:2] = Kq[:2] / 4
+        P[j, :3, :4] = Kq @ E[v, :3, :4]
+    rel = P @ torch.linalg.inv(P[0])[None]
+    rel[0] = torch.eye(4, dtype=torch.float64)
+    return rel.to(torch.float32)
+
+
+def depth_values_of(near_far_depth, n_depth=192):
+    """models/mvs/mvs_points_model.py:300-302 in its fp32 arithmetic -> [1,n_depth] on the host"""
+    near, far = (torch.tensor(float(v), dtype=torch.float32) for v in near_far_depth)
+    return (near + torch.arange(0, n_depth, dtype=torch.float32) * ((far - near) / float(n_depth)))[None, :]
+
+
+def depth_maps_from_images(mvsnet, images, intrinsics, w2cs, view_id_list, near_far_depth, n_depth=192):
+    """images [N,3,H,W] (what the dataset hands the depth estimator: ``mvs_images``), intrinsics [N,3,3] at image resolution, w2cs [N,4,4],
+    view_id_list: per depth map the indices of its views, the reference view first (the dataset's ``view_id_list``), near_far_depth = (near,
+    far) -> (depth, confidence, mask), each [len(view_id_list),H,W]: ``depth_estimators.MVSNet`` at a quarter of the resolution per reference
+    view, then the tail of gen_points (nearest up-sampling, the near / far mask, depths clamped to [near, far]).  The 2-D network runs once
+    per image, whatever number of depth maps use it."""
+    ops._need_cuda(images, "images")
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise ValueError("pointnerf_amd: images must be [N,3,H,W], got %s" % list(images.shape))
+    dev = images.device
+    H, W = images.shape[-2:]
+    dv = depth_values_of(near_far_depth, n_depth).to(dev)
+    K = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32).reshape(-1, 3, 3)
+    out = []
+    with torch.no_grad():
+        feats = mvsnet.features_of(images.float())
+        for views in view_id_list:
+            views = [int(v) for v in views]
+            proj = relative_proj_mats(intrinsics, w2cs, views)[None].to(dev)
+            d, c = mvsnet.depth_and_confidence(images[views][None], proj, dv, features=feats[views].contiguous())
+            xyz, conf, mask = ops.depth_to_cam_points(d[0], c[0], (H, W), near_far_depth, K[views[0]])
+            out.append((xyz[0, 0, 0, :, :, 2], conf[0, 0], mask[0, 0]))
+    return tuple(torch.stack(t) for t in zip(*out))
+
+
+def points_from_images(mvsnet, images, intrinsics, w2cs, view_id_list, near_far_depth, n_depth=192, **fusion):
+    """``depth_maps_from_images`` followed by ``points_from_depth_maps`` (whose keyword arguments ``fusion`` carries: geo_cnsst_num,
+    depth_conf_thresh, alphas, vox_res, ...); view_id_list must hold one entry per image, entry i with image i as its reference view
+    -> (xyz_world [M,3], confidence [M], view_id [M] int64)."""
+    if len(view_id_list) != images.shape[0] or any(int(v[0]) != i for i, v in enumerate(view_id_list)):
+        raise ValueError("pointnerf_amd: points_from_images needs one view list per image, image i first in list i")
+    depth, conf, mask = depth_maps_from_images(mvsnet, images, intrinsics, w2cs, view_id_list, near_far_depth, n_depth)
+    return points_from_depth_maps(depth, intrinsics, w2cs, conf, mask, **fusion)
 
 
 # ---- points from an external cloud (csrc/cloudinit.hip) -----------------------------------------------------------------------------

@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 SRC = os.path.join(ROOT, "pointnerf_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "_build", "emu")
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
-FILES = ["scan", "grid", "query", "aggregate", "render", "loss", "gather", "backward", "optim", "pointinit", "embed2d", "depthfuse", "cloudinit", "prof", "metrics", "probe", "raygeom", "pointmaps"]
-EXACT = {"grid", "query", "pointinit", "embed2d", "depthfuse", "cloudinit"}
+FILES = ["scan", "grid", "query", "aggregate", "render", "loss", "gather", "backward", "optim", "pointinit", "embed2d", "depthfuse", "cloudinit", "mvsdepth", "prof", "metrics", "probe", "raygeom", "pointmaps"]
+EXACT = {"grid", "query", "pointinit", "embed2d", "depthfuse", "cloudinit", "mvsdepth"}
 OPT = {}
 
 
